@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- impressions/sec of the embedding hot path at batch 65536 (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -184,7 +184,45 @@ def parse_args(argv=None):
     ap.add_argument("--secondary-timeout", type=float, default=240.0,
                     help="N>1: seconds the secondary legs (other layout, strong scaling, a2a probe) may take before the "
                          "headline line is printed without them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the LAST timed step returned (out / wide / fm) as DIR/<name>.npy; above "
+                         f"{DUMP_LIMIT_BYTES // 10**6} MB in all, a fixed seeded sample of batch rows (DIR/rows.npy lists them).  N>1: rank 0's")
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 64_000_000      # all files of one dump together, .npy headers included
+
+
+def dump_outputs(res, out_dir: str, out_cols=None) -> dict:
+    """Write the arrays a caller of the timed path receives from one step -- `res` is the step's return value: one tensor, or
+    (out, wide, fm[, ...]) with None for what the path does not produce -- as float32 / float64 .npy files; `out_cols` (optional)
+    = the columns of `out` the step writes (a padded row stride's tail is never written: not saved).  If they exceed
+    DUMP_LIMIT_BYTES together, the same fixed, seeded sample of rows (dim 0 = the batch) is kept of every array and its row
+    indices go to rows.npy, so two builds given the same arguments can be compared file for file."""
+    parts = res if isinstance(res, (tuple, list)) else (res,)
+    arrays = {}
+    for name, t in zip(("out", "wide", "fm"), parts):
+        if isinstance(t, torch.Tensor):
+            if name == "out" and out_cols is not None:
+                t = t[:, :out_cols]
+            a = t.detach().cpu().numpy()
+            arrays[name] = a.astype(np.float32 if a.dtype in (np.float16, np.float32) else np.float64, copy=False)
+    if not arrays:
+        raise SystemExit("--dump-outputs: the timed step returned no tensor")
+    rows = None
+    budget = DUMP_LIMIT_BYTES - 1024 * (len(arrays) + 1)      # room for the .npy headers
+    if sum(a.nbytes for a in arrays.values()) > budget:
+        n = min(a.shape[0] for a in arrays.values())
+        per_row = sum(a.nbytes // a.shape[0] for a in arrays.values()) + 8
+        k = max(1, min(n, budget // per_row))
+        rows = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        arrays = {name: np.ascontiguousarray(a[rows]) for name, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "arrays": {name: list(a.shape) for name, a in arrays.items()},
+            "row_sample": None if rows is None else f"{len(rows)} rows, numpy default_rng(0) without replacement, sorted (rows.npy)"}
 
 
 if __name__ == "__main__" and int(os.environ.get("WORLD_SIZE", "1")) == 1 and os.environ.get("NRX_BENCH_CHILD") != "1":
@@ -385,6 +423,8 @@ class SingleGpuPath:
             self.calls = self.wide_split_calls(check_index=True)
             self.desc += ("; headline = the gather with WideDeep.get_inp_embedding's column routing: column 0 of the 10 smallest tables -> wide "
                           "[B, 10], everything else -> deep [B, 1270] (row stride padded to 1280 floats = whole 128-byte lines, as the WideDeep model asks for)")
+        # columns of the timed launch's output that it writes (c5: 1270 of the 1280-float row stride; the last 10 are never written)
+        self.out_cols = 2 * self.width if self.cross else self.calls[0].plan.out_width
 
     def check_indices(self):
         for c in (self.fused if self.fused is not None else self.calls):
@@ -940,9 +980,10 @@ def main():
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     barrier()
     t0 = time.perf_counter()
+    last = None
     e0.record()
     for i in range(args.steps):
-        step(args.warmup + i)
+        last = step(args.warmup + i)
     e1.record()
     barrier()
     dt = time.perf_counter() - t0
@@ -951,6 +992,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     kern_ms = e0.elapsed_time(e1) / args.steps
+    # the last timed step's results, before anything else reuses its (recycled) output buffers
+    dumped = dump_outputs(last, args.dump_outputs, getattr(path, "out_cols", None)) if args.dump_outputs and rank == 0 else None
+    del last
 
     # per-step spread (outside the timed region, rank 0 / N=1 only): each step bracketed by its own pair of events
     spread = None
@@ -1240,6 +1284,7 @@ def main():
                        "output_buffer": "recycled each step (as the caching allocator does); `distinct_output_buffers` has the other mode",
                        "index_check": "on (device status word, read once after the timed region)"},
             "step_us": spread,
+            **({"dump_outputs": dumped} if dumped is not None else {}),
             # (algorithmic bytes that exceed what the HBM peak could deliver -- skewed ids over a table that fits the 256 MB Infinity Cache / the L2s:
             # most row reads never reach DRAM -- are not an HBM-roofline figure: the line says so instead of printing a fraction above 1 as "hbm")
             "roofline": {"bound": "hbm" if achieved <= HBM_PEAK_GBPS else "cache", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",

@@ -1,23 +1,22 @@
 #!/usr/bin/env python3
 """Generate golden input/output vectors by RUNNING THE REFERENCE'S OWN CODE on CPU.
 
-This script only runs in the build container (it needs /root/reference, which does not
-exist on the GPU box).  It imports the reference's modules -- with three stub modules for
+It needs a checkout of the reference project, named by NRX_REFERENCE_DIR (the suite never runs this script: the
+fixtures it wrote are committed).  It imports the reference's modules -- with three stub modules for
 the packages the image lacks (omegaconf / lightning / pytorch_lightning; they only touch
 config + trainer plumbing, all arithmetic is the reference's code on genuine torch) -- and
 writes small .npz fixtures next to this file.  No reference source is copied: the fixtures
 hold tensors only (weights, index batches, outputs, gradients).
 
-    python tests/golden/gen_golden.py          # rewrites tests/golden/*.npz
-    python tests/golden/gen_golden.py --check  # regenerates into a temp dir and compares with the committed fixtures
+    NRX_REFERENCE_DIR=<checkout> python tests/golden/gen_golden.py          # rewrites tests/golden/*.npz
+    NRX_REFERENCE_DIR=<checkout> python tests/golden/gen_golden.py --check  # regenerates into a temp dir and compares with the committed fixtures
 
 Reproducibility: the reference iterates Python sets of feature names (base_model.py:85-90), so the order in which its
 modules register parameters -- and with it which random numbers land in which table -- follows the process's string-hash
 seed.  The script therefore pins PYTHONHASHSEED=0 by re-executing itself before anything is imported (no GPU is involved),
-and randomises parameters in sorted-name order; two runs give bit-identical arrays (checked by --check and by
-tests/test_golden_reproducible.py).
+and randomises parameters in sorted-name order; two runs give bit-identical arrays (checked by --check).
 
-Reference entry points exercised (paths relative to /root/reference):
+Reference entry points exercised (paths relative to the reference checkout):
   src/model/BaseModel/base_model.py:262-308   get_feature_embedding / array_feature_pooling /
                                               get_embeddings_from_batch
   src/model/sort/deep/model.py:12-43          DeepModel / Deep.forward
@@ -48,7 +47,7 @@ import yaml
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = HERE                      # --check writes to a temp dir instead
 CFG = os.path.join(HERE, "configs")
-REF = "/root/reference"
+REF = os.environ.get("NRX_REFERENCE_DIR", "")
 
 
 # --------------------------------------------------------------------------- stubs
@@ -495,8 +494,8 @@ def compare_dirs(ref_dir, new_dir):
 
 
 if __name__ == "__main__":
-    if not os.path.isdir(REF):
-        sys.exit("needs /root/reference (build container only)")
+    if not REF or not os.path.isdir(REF):
+        sys.exit("set NRX_REFERENCE_DIR to a checkout of the reference project")
     install_stubs()
     if "--check" in sys.argv[1:]:
         with tempfile.TemporaryDirectory() as tmp:

@@ -347,7 +347,10 @@ class PreparedShardedStep:
     def check(self):
         """Raise IndexError if a lookup of a run since the last check() named a row outside its table on ANY rank (every rank raises together: one
         small all-reduce + one host read), RuntimeError if a block overflowed its capacity (lookups were dropped: redo with a larger slack).
-        Call it off the hot path -- shard_model_step_ does every 64th step."""
+        Call it off the hot path.  shard_model_step_ runs it right after the forward of a bound step's FIRST call (before any backward or
+        optimizer step of it) and then on calls 65, 129, ...: calls 2..64 of a step (and the calls after each check until the next one) can still
+        be applied -- backward and optimizer on the truncated lookups -- before an overflow in them surfaces; check_shard_steps(model) covers them
+        at epoch end or teardown."""
         bad = torch.zeros(2, dtype=torch.int64, device=self.groups[0]["dev"] if self.groups else "cpu")
         if self.status is not None:
             bad[0] = self.status[0].to(torch.int64)
@@ -629,7 +632,11 @@ def shard_model_step_(model, rank: int, world: int, group=None, host_staged: boo
     (sharding.allreduce_dense_grads(sharding.data_parallel_params(model), world)).  state_dict keys are unchanged; the table values are the
     arenas (full_state_dict / load_full_state_dict_ convert to and from the reference's full tables).
     binary_masks: the array features' masks are 0/1 (DataReader's, src/dataset/DataReader/data_reader.py:96-109).
-    grad_average: scale the table gradients by 1 / world (every rank's loss is a mean over its own batch)."""
+    grad_average: scale the table gradients by 1 / world (every rank's loss is a mean over its own batch).
+    Overflow and out-of-range ids: a bound step is checked (PreparedShardedStep.check, on every rank together) right after the forward of its
+    first call, so such a batch raises before anything is applied; later calls are checked every 64th call only -- calls 2..64 of a step, and
+    the calls between two checks after that, can apply a backward and optimizer step on dropped lookups before the next check raises.  Call
+    check_shard_steps(model) at epoch end and at teardown to surface what the last calls left."""
     import torch.nn as nn
     from .sharding import RowShardedEmbedding, ShardedFeature
     eng = RowShardedEmbedding(rank, world, group, None, slack=slack, host_staged=host_staged, overflow_policy="defer")
@@ -681,14 +688,26 @@ def shard_model_step_(model, rank: int, world: int, group=None, host_staged: boo
             if w_ is not None:
                 w_.copy_(batch[m])
         step._calls += 1
-        if step._calls % 64 == 1 and step._calls > 1:       # deferred: out-of-range ids / dropped lookups of the last 64 steps surface here, on every rank
+        if step._calls % 64 == 1 and step._calls > 1:       # deferred: out-of-range ids / dropped lookups of the last 64 calls surface here, on every rank
             step.check()
         if torch.is_grad_enabled():
             out, fmv = _ShardedStepFn.apply(step, model._sparse_sink, scale, need_out, bool(fm), anchor)
         else:
             o, _, f_ = step.run()
             out, fmv = (o if need_out else None), (f_ if fm else None)
+        if step._calls == 1:
+            # a key's first call is checked at once (one all-reduce + one host read per new key): a batch whose blocks overflow raises here, on
+            # every rank, before its backward and optimizer step.  Calls 2..64 are only checked on call 65 (or by check_shard_steps).
+            step.check()
         return out, None, fmv, list(dims), list(present)
 
     model._embed = _embed_step
     return model
+
+
+def check_shard_steps(model):
+    """PreparedShardedStep.check() on every step bound by shard_model_step_ (in binding order, so every rank runs the same collectives): raises
+    IndexError / RuntimeError for the out-of-range ids and overflowed blocks recorded since each step's last check.  For epoch end and teardown --
+    the calls after a step's last periodic check are otherwise never checked."""
+    for step, *_ in getattr(model, "_shard_steps", {}).values():
+        step.check()

@@ -461,3 +461,101 @@ def test_a_table_with_fewer_rows_than_ranks_leaves_an_empty_shard_that_works():
             seen[k] = v
     assert ("tiny", 1) in seen and ("tiny", 0) not in seen                 # row 0 is the padding row: it never trains
     np.testing.assert_allclose(seen[("tiny", 1)], g_tiny, rtol=1e-5, atol=1e-5)
+
+
+# ---------------------------------------------------------------------------------------------- a batch that overflows an exchange block
+def _model_overflow_worker(rank, world, port, q):
+    import os
+    from news_recsys_amd import sharding
+    from news_recsys_amd.model.sort.fm.model import FM
+    from tests.conftest import CONFIGS, GOLDEN
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from tests import _poison
+    _poison.poison()          # (NRX_TEST_POISON=1: this rank's buffers start from 0xFF bytes)
+    res = {}
+    try:
+        g = dict(np.load(os.path.join(GOLDEN, "model_fm.npz"), allow_pickle=False))
+        m = FM(os.path.join(CONFIGS, "cf_fm_small.yaml"))
+        m.load_state_dict({k[6:]: torch.from_numpy(v) for k, v in g.items() if k.startswith("param/")}, strict=True)
+        m = m.to(DEV)
+        shard_step.shard_model_step_(m, rank, world, host_staged=True)              # the default slack (0.05)
+        full = {k[6:]: torch.from_numpy(v) for k, v in g.items() if k.startswith("batch/")}
+        opt = m.configure_optimizers()["optimizer"]
+
+        def train(batch):
+            opt.zero_grad()
+            m.bceLoss(m(batch), batch["label"][:, 0]).backward()
+            grads = [p.grad for p in sharding.data_parallel_params(m) if p.grad is not None]
+            flat = torch.cat([x.reshape(-1) for x in grads]).cpu()
+            dist.all_reduce(flat)
+            flat /= world
+            off = 0
+            for x in grads:
+                x.copy_(flat[off:off + x.numel()].view_as(x))
+                off += x.numel()
+            opt.step()
+
+        n = next(iter(full.values())).shape[0] // world
+        train({k: v[rank * n:(rank + 1) * n].contiguous().to(DEV) for k, v in full.items()})      # a clean batch: trains, checks clean
+        shard_step.check_shard_steps(m)
+        res["clean"] = True
+        # 1024 samples per rank whose item ids are all even rows: every rank's item_id lookups go to rank 0, past the block capacity
+        # (capf = 640 at the default slack)
+        big = {k: v.repeat((1024 * world + v.shape[0] - 1) // v.shape[0], *[1] * (v.dim() - 1))[:1024 * world] for k, v in full.items()}
+        big["item_id"] = big["item_id"] // 2 * 2
+        skew = {k: v[rank * 1024:(rank + 1) * 1024].contiguous().to(DEV) for k, v in big.items()}
+        before = {k: v.detach().clone() for k, v in m.state_dict().items()}
+        try:
+            train(skew)
+            res["raised"] = False
+        except RuntimeError as e:
+            res["raised"] = "overflowed" in str(e)
+        torch.cuda.synchronize()
+        res["unchanged"] = all(torch.equal(v, before[k]) for k, v in m.state_dict().items())
+        with torch.no_grad():                                     # the key's second call is not checked at the call ...
+            m(skew)
+        try:                                                      # ... check_shard_steps (epoch end, teardown) surfaces it
+            shard_step.check_shard_steps(m)
+            res["later"] = False
+        except RuntimeError:
+            res["later"] = True
+        q.put((rank, res))
+        dist.barrier()
+    except Exception as e:
+        q.put((rank, {**res, "error": f"{type(e).__name__}: {e}"[:500]}))
+        raise
+    finally:
+        dist.destroy_process_group()
+
+
+def test_bound_sharded_model_raises_on_an_overflowing_batch_before_it_trains():
+    """shard_model_step_ at world 2, default slack: a batch whose item ids all fall on rank 0 overflows that block in nrx_route_feat.  Its first
+    training step raises RuntimeError on both ranks right after the forward -- before backward and optimizer: every arena and parameter keeps
+    its bits -- and check_shard_steps(model) raises for a later call of that step that nothing checked at the call, while a clean batch trains
+    and checks clean."""
+    world = 2
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_model_overflow_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = {}
+    try:
+        for _ in range(world):
+            item = q.get(timeout=300)
+            res[item[0]] = item[1]
+        for p in procs:
+            p.join(timeout=120)
+    finally:
+        for p in procs:                                   # (a rank that failed leaves its peer waiting in a collective)
+            if p.is_alive():
+                p.kill()
+                p.join(timeout=30)
+    for r in range(world):
+        got = res[r]
+        assert "error" not in got, (r, got)
+        assert got["clean"] and got["raised"] and got["unchanged"] and got["later"], (r, got)
+    assert all(p.exitcode == 0 for p in procs)

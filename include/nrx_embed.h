@@ -89,6 +89,12 @@ typedef struct nrx_feature {
  * lookups outnumber the rows they name many times over (a bag feature flattened into one pseudo-feature: the sharded step's pooled channel) -- rows
  * leave the in-order walk for the wavefront-per-chunk work lists from 32 lookups on, as in a launch with bag features, instead of 16. */
 #define NRX_FEAT_MANY_PER_ROW 4
+/* nrx_feature.flags: `table` holds bf16 [rows, dim] (uint16 bit patterns, widened to fp32 on load -- exact) instead of fp32.  Describes the
+ * FORWARD's table only: honoured by nrx_embed_fwd / nrx_embed_fwd_train (every kernel family: the result is bit-identical to the fp32 call on
+ * the widened table); the backward entry points ignore it (their `table` is an fp32 gradient table, or unread); an entry point that reads
+ * `table` as fp32 and has no bf16 form (nrx_embed_dcn_v1_fwd) returns NRX_ERR_UNSUPPORTED when it is set.  Tables then train with
+ * nrx_sparse_adam_step_bf16. */
+#define NRX_FEAT_TABLE_BF16 8
 
 /* ---- library ---------------------------------------------------------------------------- */
 NRX_API int nrx_abi_version(void);
@@ -328,6 +334,22 @@ NRX_API int nrx_sparse_adam_step(float* const* tables, float* const* exp_avg, fl
                          int32_t dim, const int64_t* uniq_keys, const float* grads, int64_t n_unique,
                          const int64_t* n_unique_dev, float step_size, const float* step_size_dev, float beta1,
                          float beta2, float eps, float lr_times_weight_decay, void* stream);
+
+/* nrx_sparse_adam_step for bf16 tables (uint16 bit patterns [rows, dim]; moments stay fp32, in the same layouts): the stored weight is widened,
+ * the fp32 step is applied with the same arithmetic in the same order (the moments leave exactly as nrx_sparse_adam_step leaves them on the
+ * widened table), and the new weight is rounded to bf16 STOCHASTICALLY:
+ *   bits16 = (uint16) (h >> 48),   h = mix(mix(mix(mix(mix(seed) ^ step) ^ table) ^ row) ^ col)
+ *   mix(z)  = splitmix64's finaliser of z + 0x9E3779B97F4A7C15:  z += 0x9E37..15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *             z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31
+ *   bf16    = (f32_bits(w) + bits16) >> 16          (finite w; inf / NaN take a plain truncating cast, a NaN stays a NaN)
+ * -- stateless and counter-based: the bits depend on (seed, step, table, row, column) only, so the result does not depend on the launch
+ * shape or on the order of the unique rows, a captured loop replays the same stream, and a resumed run continues it.  step: the optimizer
+ * step index; step_dev (optional, device int64[1]) is read instead (captured loops). */
+NRX_API int nrx_sparse_adam_step_bf16(uint16_t* const* tables, float* const* exp_avg, float* const* exp_avg_sq, int32_t n_tables,
+                         int32_t dim, const int64_t* uniq_keys, const float* grads, int64_t n_unique,
+                         const int64_t* n_unique_dev, float step_size, const float* step_size_dev, float beta1,
+                         float beta2, float eps, float lr_times_weight_decay, uint64_t sr_seed, int64_t step,
+                         const int64_t* step_dev, void* stream);
 
 /* Exact dense AdamW from row-sparse gradients ("exact-dense mode").  The reference trains every embedding table with one dense
  * torch.optim.AdamW over model.parameters() (src/model/sort/deep/model.py:54-65): every row moves every step.  nrx_rows_mark writes, for every

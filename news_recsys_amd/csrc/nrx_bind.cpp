@@ -61,13 +61,15 @@ struct BoundPlan {
             PyObject* o = PyList_GET_ITEM(tables, i);
             if (!THPVariable_Check(o)) return false;
             const at::Tensor& t = THPVariable_Unpack(o);
-            if (!t.is_cuda() || t.scalar_type() != at::kFloat || t.dim() != 2 || !t.is_contiguous()) return false;
+            if (!t.is_cuda() || (t.scalar_type() != at::kFloat && t.scalar_type() != at::kBFloat16) || t.dim() != 2 || !t.is_contiguous()) return false;
             ts[(size_t)i] = &t;
         }
         for (size_t i = 0; i < f.size(); ++i) {
             const int k = table_of[i];
             if (f[i].kind == NRX_DENSE) { f[i].table = nullptr; f[i].rows = 0; continue; }
             if (k < 0 || k >= nt) return false;
+            // a bf16 table is read as bf16 only by slots that say so (NRX_FEAT_TABLE_BF16); a mismatch is the Python path's error to raise
+            if ((ts[(size_t)k]->scalar_type() == at::kBFloat16) != ((f[i].flags & NRX_FEAT_TABLE_BF16) != 0)) return false;
             f[i].table = static_cast<const float*>(ts[(size_t)k]->data_ptr());
             f[i].rows = ts[(size_t)k]->size(0);
         }

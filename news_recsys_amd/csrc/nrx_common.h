@@ -48,6 +48,10 @@ int nrx_zero2_async(void* p, size_t bytes_p, void* q, size_t bytes_q, hipStream_
     } while (0)
 
 static inline bool nrx_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// a forward table's alignment for 4-column loads: 16 bytes for fp32 rows, 8 for bf16 ones (NRX_FEAT_TABLE_BF16)
+static inline bool nrx_table_aligned(const nrx_feature_t& s) {
+    return (reinterpret_cast<uintptr_t>(s.table) & ((s.flags & NRX_FEAT_TABLE_BF16) ? 7u : 15u)) == 0;
+}
 
 // Device-side feature descriptor (48 B; 64 of them fit the 4 KiB kernarg segment).
 struct FeatDev {
@@ -62,9 +66,17 @@ struct FeatDev {
     uint8_t kind;
     uint8_t idx64;
     uint8_t fm;
-    uint8_t flags;          // NRX_FEAT_* bits (ROW0_IS_DATA, BAG_CSR)
+    uint8_t flags;          // NRX_FEAT_* bits (ROW0_IS_DATA, BAG_CSR; TABLE_BF16 in the forward)
 };
 static_assert(sizeof(FeatDev) == 48, "FeatDev must stay 48 bytes");
+
+// bf16 -> fp32 widening (exact: the bf16 pattern becomes the high half of the fp32 one).  One definition for every kernel that reads
+// bf16 tables (NRX_FEAT_TABLE_BF16): one element, or four packed in two dwords (element 0 in the low half of `lo`).
+__device__ __forceinline__ float nrx_bf16_to_f32(uint32_t h16) { return __builtin_bit_cast(float, h16 << 16); }
+__device__ __forceinline__ float4 nrx_bf16x4_to_f32(uint32_t lo, uint32_t hi) {
+    return make_float4(__builtin_bit_cast(float, lo << 16), __builtin_bit_cast(float, lo & 0xFFFF0000u),
+                       __builtin_bit_cast(float, hi << 16), __builtin_bit_cast(float, hi & 0xFFFF0000u));
+}
 
 // Address-space helpers.  Kernel arguments that are indexed dynamically are read through an
 // explicit constant-address-space (4) pointer to the kernarg segment (scalar s_load with a uniform

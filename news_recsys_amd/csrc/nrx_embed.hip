@@ -71,6 +71,40 @@ __device__ __forceinline__ float4 load_row4(const float* table, int64_t id, int 
     return v;
 }
 
+// bf16 tables (NRX_FEAT_TABLE_BF16, the HB = true instantiations only): 4 columns as 8 bytes (2-byte elements where dim % 4 != 0),
+// widened in registers -- exact, so every result equals the fp32 kernels' on the widened table.  The storage test is on a kernarg
+// descriptor: wave-uniform in the big kernels, and made once per feature, outside the unrolled bag loop (bag_rows_bf16).
+template <bool HB>
+__device__ __forceinline__ bool feat_bf16(const FeatDev& f) { return HB && (f.flags & NRX_FEAT_TABLE_BF16) != 0; }
+// whole-chunk loads allowed: dim % 4 == 0 and rows aligned for them (16 B fp32, 8 B bf16)
+template <bool HB>
+__device__ __forceinline__ bool table_vec(const FeatDev& f, int D) {
+    if (!HB) return ((D & 3) == 0) && ((reinterpret_cast<uintptr_t>(f.table) & 15u) == 0);
+    return ((D & 3) == 0) && ((reinterpret_cast<uintptr_t>(f.table) & (feat_bf16<HB>(f) ? 7u : 15u)) == 0);
+}
+// load_row4 with the storage known at compile time (BF: the table is bf16)
+template <bool BF>
+__device__ __forceinline__ float4 load_row4_s(const float* table, int64_t id, int D, int k0, bool vec) {
+    if (!BF) return load_row4(table, id, D, k0, vec);
+    const uint16_t* p = reinterpret_cast<const uint16_t*>(table) + id * (int64_t)D + k0;
+    if (vec) {
+        const uint2 t = *reinterpret_cast<const uint2*>(p);
+        return nrx_bf16x4_to_f32(t.x, t.y);
+    }
+    float4 v;
+    v.x = nrx_bf16_to_f32(p[0]);
+    v.y = (k0 + 1 < D) ? nrx_bf16_to_f32(p[1]) : 0.f;
+    v.z = (k0 + 2 < D) ? nrx_bf16_to_f32(p[2]) : 0.f;
+    v.w = (k0 + 3 < D) ? nrx_bf16_to_f32(p[3]) : 0.f;
+    return v;
+}
+// one load, the storage read from the descriptor (a single row: the branch costs nothing a loop would repeat)
+template <bool HB>
+__device__ __forceinline__ float4 load_row4_t(const FeatDev& f, int64_t id, int D, int k0, bool vec) {
+    if (feat_bf16<HB>(f)) return load_row4_s<true>(f.table, id, D, k0, vec);
+    return load_row4(f.table, id, D, k0, vec);
+}
+
 // Entry `pos` of sample b's bag as the raw (id, weight) the pooling uses.  Padded form: ids [B, L] + optional weights.
 // CSR form (NRX_FEAT_BAG_CSR): f.weight holds int64 offsets [B + 1]; real entries weigh 1, the positions past the bag's
 // end are what DataReader pads with -- id 0, mask 0 (weight 1 for NRX_BAG_MEAN, whose padded form has no mask).
@@ -94,10 +128,75 @@ __device__ __forceinline__ void bag_entry(const FeatDev& f, int64_t b, int s, co
     }
 }
 
+// One lane's share of a bag over a bf16 table: the sample's staged (id, weight) entries row[0 .. cur), pooled into acc / den in entry order --
+// embed_fwd_generic's fp32 bag loop with the storage fixed at compile time, so the U row loads of a pass stay unconditional (see inside).
+__device__ __forceinline__ void bag_rows_bf16(const float* table, const BagPair* row, int cur, int D, int k0, bool vec_load, float4& acc, float& den) {
+    constexpr int U = 8;
+    int l = 0;
+    // 16-byte-aligned tables (every reference shape): the U row loads of a pass are issued unconditionally -- an entry with
+    // weight 0 reads row 0 and its value is replaced by zeros where it is USED.  A load behind `if (w != 0)` is a branch around
+    // a load: the compiler then waits vmcnt(0) in front of every one of them and the eight loads go out one behind the other
+    // (seen in the ISA); so does the aligned / unaligned choice inside load_row4 when it is made per load.
+    if (vec_load) {
+        for (; l + U <= cur; l += U) {
+            BagPair p[U];
+            float4 r[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) p[u] = row[l + u];
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                r[u] = load_row4_s<true>(table, (int64_t)(p[u].w != 0.f ? p[u].id : 0), D, k0, true);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+#pragma clang fp contract(off)
+                const bool on = p[u].w != 0.f;
+                const float rx = on ? r[u].x : 0.f, ry = on ? r[u].y : 0.f, rz = on ? r[u].z : 0.f, rw = on ? r[u].w : 0.f;
+                den += p[u].w;
+                acc.x += rx * p[u].w;
+                acc.y += ry * p[u].w;
+                acc.z += rz * p[u].w;
+                acc.w += rw * p[u].w;
+            }
+        }
+    }
+    for (; l + U <= cur; l += U) {
+        BagPair p[U];
+        float4 r[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) p[u] = row[l + u];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            r[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (p[u].w != 0.f) r[u] = load_row4_s<true>(table, p[u].id, D, k0, vec_load);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma clang fp contract(off)
+            den += p[u].w;
+            acc.x += r[u].x * p[u].w;
+            acc.y += r[u].y * p[u].w;
+            acc.z += r[u].z * p[u].w;
+            acc.w += r[u].w * p[u].w;
+        }
+    }
+    for (; l < cur; ++l) {
+#pragma clang fp contract(off)
+        const BagPair p = row[l];
+        den += p.w;
+        if (p.w != 0.f) {
+            const float4 r = load_row4_s<true>(table, p.id, D, k0, vec_load);
+            acc.x += r.x * p.w;
+            acc.y += r.y * p.w;
+            acc.z += r.z * p.w;
+            acc.w += r.w * p.w;
+        }
+    }
+}
+
 // --------------------------------------------------------------------------------------------
 // Generic forward: any mix of sparse / dense / bag features, any dims, wide routing, FM.
 // --------------------------------------------------------------------------------------------
-template <int QLOG2>
+template <int QLOG2, bool HB>     // HB: some table of the launch is bf16
 __global__ __launch_bounds__(NRX_BLOCK) void embed_fwd_generic(const EmbedArgs a) {
     constexpr int Q = 1 << QLOG2;
     constexpr int TB = NRX_BLOCK / Q;
@@ -130,7 +229,8 @@ __global__ __launch_bounds__(NRX_BLOCK) void embed_fwd_generic(const EmbedArgs a
         for (int s2 = 0; s2 < NPRE; ++s2) pre_feat[s2] = -1;
         for (int fi = 0; fi < a.n && ns < NPRE; ++fi) {
             const FeatDev& f = a.f[fi];
-            if (f.kind == NRX_SPARSE && f.dim <= 4 * Q && (f.dim & 3) == 0 && (reinterpret_cast<uintptr_t>(f.table) & 15u) == 0) {
+            if (f.kind == NRX_SPARSE && f.dim <= 4 * Q && (f.dim & 3) == 0 &&
+                (reinterpret_cast<uintptr_t>(f.table) & (feat_bf16<HB>(f) ? 7u : 15u)) == 0) {
 #pragma unroll
                 for (int s2 = 0; s2 < NPRE; ++s2)
                     if (s2 == ns) pre_feat[s2] = fi;
@@ -152,7 +252,10 @@ __global__ __launch_bounds__(NRX_BLOCK) void embed_fwd_generic(const EmbedArgs a
                     if (q == 0 && live) nrx_report_oob(a.status, a.feat_id[pre_feat[s2]], b, pid[s2]);
                     pid[s2] = 0;
                 }
-                if (live && q * 4 < f.dim) pre_row[s2] = *reinterpret_cast<const float4*>(f.table + pid[s2] * (int64_t)f.dim + q * 4);
+                if (live && q * 4 < f.dim) {
+                    if (feat_bf16<HB>(f)) pre_row[s2] = load_row4_s<true>(f.table, pid[s2], f.dim, q * 4, true);
+                    else pre_row[s2] = *reinterpret_cast<const float4*>(f.table + pid[s2] * (int64_t)f.dim + q * 4);
+                }
             }
         }
     }
@@ -160,7 +263,7 @@ __global__ __launch_bounds__(NRX_BLOCK) void embed_fwd_generic(const EmbedArgs a
     for (int fi = 0; fi < a.n; ++fi) {
         const FeatDev& f = a.f[fi];
         const int D = f.dim;
-        const bool vec_load = ((D & 3) == 0) && ((reinterpret_cast<uintptr_t>(f.table) & 15u) == 0);
+        const bool vec_load = table_vec<HB>(f, D);
         for (int kc = 0; kc < D; kc += 4 * Q) {
             const int k0 = kc + q * 4;
             const bool active = live && k0 < D;
@@ -178,7 +281,7 @@ __global__ __launch_bounds__(NRX_BLOCK) void embed_fwd_generic(const EmbedArgs a
                         if (q == 0) nrx_report_oob(a.status, a.feat_id[fi], b, id);
                         id = 0;
                     }
-                    v = load_row4(f.table, id, D, k0, vec_load);
+                    v = load_row4_t<HB>(f, id, D, k0, vec_load);
                 }
             } else if (f.kind == NRX_DENSE) {
                 if (active && k0 == 0)
@@ -293,7 +396,9 @@ __global__ __launch_bounds__(NRX_BLOCK) void embed_fwd_generic(const EmbedArgs a
                         s_bag[s * stride + l] = p;
                     }
                     __syncthreads();
-                    if (active) {
+                    if (active && feat_bf16<HB>(f)) {
+                        bag_rows_bf16(f.table, s_bag + sb * stride, cur, D, k0, vec_load, acc, den);     // bf16: the same loop, storage fixed at compile time
+                    } else if (active) {
                         const BagPair* row = s_bag + sb * stride;
                         constexpr int U = 8;
                         int l = 0;
@@ -429,6 +534,7 @@ __device__ __forceinline__ float group_sum_rt(float v) { return group_sum<Q>(v);
 // static LDS of embed_fwd_small_kernel (its copy of the descriptors), counted by the launcher's 64 KB eligibility test
 #define NRX_SMALL_STATIC_LDS (NRX_MAX_FEATURES * sizeof(FeatDev))
 
+template <bool HB>     // HB: some table of the launch is bf16
 __global__ __launch_bounds__(NRX_BLOCK) void embed_fwd_small_kernel(const EmbedArgs args_in_kernarg) {
     const NRX_CONST EmbedArgs* a = nrx_kernarg<EmbedArgs>();
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -501,7 +607,10 @@ __global__ __launch_bounds__(NRX_BLOCK) void embed_fwd_small_kernel(const EmbedA
                 if (c == 0) nrx_report_oob(a->status, a->feat_id[fi], b, id);
                 id = 0;
             }
-            if (!bag || w != 0.f) v = *reinterpret_cast<const float4*>(f.table + id * (int64_t)f.dim + 4 * c);
+            if (!bag || w != 0.f) {
+                if (feat_bf16<HB>(f)) v = load_row4_s<true>(f.table, id, f.dim, 4 * c, true);
+                else v = *reinterpret_cast<const float4*>(f.table + id * (int64_t)f.dim + 4 * c);
+            }
         }
         s_rows[t] = v;
         s_wt[t] = w;
@@ -2335,6 +2444,18 @@ int pack_features(const nrx_feature_t* feats, int32_t n, EmbedArgs& a, int& max_
     return NRX_OK;
 }
 
+// The forward's storage bit (pack_features keeps only the bits every kernel family reads, so the backward never sees it): true when
+// some table of the launch is bf16 -- the launch then takes the kernels' bf16-capable instantiation.
+bool mark_bf16_tables(const nrx_feature_t* feats, int32_t n, EmbedArgs& a) {
+    bool any = false;
+    for (int i = 0; i < n; ++i)
+        if (feats[i].kind != NRX_DENSE && (feats[i].flags & NRX_FEAT_TABLE_BF16)) {
+            a.f[i].flags |= (uint8_t)NRX_FEAT_TABLE_BF16;
+            any = true;
+        }
+    return any;
+}
+
 #define NRX_QSWITCH(qlog2, ...)               \
     switch (qlog2) {                           \
         case 0: { constexpr int QL = 0; __VA_ARGS__; } break; \
@@ -2363,25 +2484,26 @@ void plan_generic(int max_dim, int max_bag, int& qlog2, int& lds_chunk, size_t& 
 }
 
 // Uniform features (all single-valued, one D = 4Q): the ring kernel of nrx_embed_ring.h.  R = rows in flight per lane.
-template <int QLOG2, int R, bool NT>
+template <int QLOG2, int R, bool NT, typename TS>
 void launch_ring_r(const UniformArgs& ua, int64_t batch, bool fm, bool store, hipStream_t st) {
     constexpr int TB = NRX_BLOCK >> QLOG2;
     const dim3 grid((unsigned)((batch + TB - 1) / TB)), block(NRX_BLOCK);
     const size_t lds = (size_t)ua.n * TB * sizeof(int32_t);
-    if (fm && store) hipLaunchKernelGGL((embed_fwd_ring<QLOG2, R, true, true, NT>), grid, block, lds, st, ua);
-    else if (fm) hipLaunchKernelGGL((embed_fwd_ring<QLOG2, R, true, false, NT>), grid, block, lds, st, ua);
-    else hipLaunchKernelGGL((embed_fwd_ring<QLOG2, R, false, true, NT>), grid, block, lds, st, ua);
+    if (fm && store) hipLaunchKernelGGL((embed_fwd_ring<QLOG2, R, true, true, NT, 4, TS>), grid, block, lds, st, ua);
+    else if (fm) hipLaunchKernelGGL((embed_fwd_ring<QLOG2, R, true, false, NT, 4, TS>), grid, block, lds, st, ua);
+    else hipLaunchKernelGGL((embed_fwd_ring<QLOG2, R, false, true, NT, 4, TS>), grid, block, lds, st, ua);
 }
 
-template <int QLOG2>
+// TS: the storage of every table of the launch (float, or uint16_t = bf16; the host groups features by (dim, storage))
+template <int QLOG2, typename TS = float>
 void launch_uniform(const UniformArgs& ua, int64_t batch, bool fm, bool store, hipStream_t st) {
     const int n = ua.n;
     // non-temporal row loads once the launch's tables exceed the 256 MiB Infinity Cache (cache-resident tables lose
     // 15-30 % with them, DRAM-resident ones gain 5-8 %)
     int64_t table_bytes = 0;
-    for (int i = 0; i < n; ++i) table_bytes += ua.rows[i] * (int64_t)(16 << QLOG2);
+    for (int i = 0; i < n; ++i) table_bytes += ua.rows[i] * (int64_t)((4 * (int)sizeof(TS)) << QLOG2);
     const bool nt = table_bytes > (256ll << 20);
-#define NRX_LR(R_) (nt ? launch_ring_r<QLOG2, R_, true>(ua, batch, fm, store, st) : launch_ring_r<QLOG2, R_, false>(ua, batch, fm, store, st))
+#define NRX_LR(R_) (nt ? launch_ring_r<QLOG2, R_, true, TS>(ua, batch, fm, store, st) : launch_ring_r<QLOG2, R_, false, TS>(ua, batch, fm, store, st))
     // ring depth: 8 rows in flight per lane, except 64-byte rows streamed from DRAM (C2), where 4 measured 2-3 % faster
     // with a recycled output buffer (57.7 vs 59.1 us; profiles/r02_c2_ring_sweep.md)
     if (n >= 8 && !(QLOG2 == 2 && nt)) NRX_LR(8);
@@ -2441,7 +2563,7 @@ extern "C" int nrx_embed_fwd_train(const nrx_feature_t* feats, int32_t n_feats, 
         for (int i = 0; i < n_feats && ok; ++i) {
             const nrx_feature_t& s = feats[i];
             ok = s.wide_col < 0 && !(s.flags & NRX_FEAT_BAG_CSR) && s.kind >= NRX_SPARSE && s.kind <= NRX_BAG_SUM;
-            if (s.kind != NRX_DENSE) ok = ok && s.table != nullptr && (s.dim & 3) == 0 && nrx_aligned16(s.table) && s.dim >= 4;
+            if (s.kind != NRX_DENSE) ok = ok && s.table != nullptr && (s.dim & 3) == 0 && nrx_table_aligned(s) && s.dim >= 4;
             if (s.kind == NRX_BAG_MASKED_MEAN) ok = ok && s.weight != nullptr;
             const int64_t L = s.kind >= NRX_BAG_MASKED_MEAN ? s.bag_len : 1, c = s.kind == NRX_DENSE ? 1 : s.dim / 4;
             items += L * c;
@@ -2463,6 +2585,7 @@ extern "C" int nrx_embed_fwd_train(const nrx_feature_t* feats, int32_t n_feats, 
             int max_dim, max_bag;
             int rc = pack_features(feats, n_feats, a, max_dim, max_bag, "nrx_embed_fwd");
             if (rc != NRX_OK) return rc;
+            const bool hb = mark_bf16_tables(feats, n_feats, a);
             for (int i = 0; i < NRX_MAX_FEATURES; ++i) a.feat_id[i] = (uint8_t)i;
             a.batch = batch; a.out = out; a.out_ld = out_ld; a.wide = nullptr; a.wide_ld = 0;
             a.fm_out = fm_fields > 0 ? fm_out : nullptr;
@@ -2472,7 +2595,8 @@ extern "C" int nrx_embed_fwd_train(const nrx_feature_t* feats, int32_t n_feats, 
             a.status = status;
             a.n = n_feats;
             a.lds_chunk = 0;
-            hipLaunchKernelGGL(embed_fwd_small_kernel, dim3((unsigned)batch), dim3(NRX_BLOCK), smem_small, st, a);
+            if (hb) hipLaunchKernelGGL(embed_fwd_small_kernel<true>, dim3((unsigned)batch), dim3(NRX_BLOCK), smem_small, st, a);
+            else hipLaunchKernelGGL(embed_fwd_small_kernel<false>, dim3((unsigned)batch), dim3(NRX_BLOCK), smem_small, st, a);
             NRX_LAUNCH_CHECK("nrx_embed_fwd(small batch)");
             return NRX_OK;
         }
@@ -2485,24 +2609,25 @@ extern "C" int nrx_embed_fwd_train(const nrx_feature_t* feats, int32_t n_feats, 
     auto eligible = [&](const nrx_feature_t& s) {
         const int q = s.dim / 4;
         return s.kind == NRX_SPARSE && s.wide_col < 0 && s.index_bits == feats[0].index_bits && s.table != nullptr &&
-               nrx_aligned16(s.table) && s.rows >= 1 && (s.dim & 3) == 0 && q >= 4 && q <= 64 && (q & (q - 1)) == 0;
+               nrx_table_aligned(s) && s.rows >= 1 && (s.dim & 3) == 0 && q >= 4 && q <= 64 && (q & (q - 1)) == 0;
     };
     // (first columns that are no multiple of 4 floats -- a dense value earlier in the sorted order -- and an unaligned `out` take the
     // ring kernel's dword-aligned store form: UniformArgs::unal; they used to drop to the generic kernel, 0.33 vs 0.6+ of peak)
     const bool out_ok = true;
     const bool out_al = (out == nullptr) || (nrx_aligned16(out) && (out_ld & 3) == 0);
     int n_fm = 0, n_dims = 0, n_el = 0;
-    int dims_seen[8];
+    int dims_seen[8];                      // uniform groups, keyed by (dim, storage): 2 * dim + (bf16 table)
     bool el[NRX_MAX_FEATURES];
+    auto group_key = [](const nrx_feature_t& s) { return 2 * s.dim + ((s.flags & NRX_FEAT_TABLE_BF16) ? 1 : 0); };
     for (int i = 0; i < n_feats; ++i) {
         n_fm += feats[i].fm_field != 0;
         el[i] = out_ok && eligible(feats[i]);
         if (!el[i]) continue;
         int j = 0;
-        while (j < n_dims && dims_seen[j] != feats[i].dim) ++j;
+        while (j < n_dims && dims_seen[j] != group_key(feats[i])) ++j;
         if (j == n_dims) {
             if (n_dims == 8) { el[i] = false; continue; }
-            dims_seen[n_dims++] = feats[i].dim;
+            dims_seen[n_dims++] = group_key(feats[i]);
         }
         ++n_el;
     }
@@ -2520,14 +2645,15 @@ extern "C" int nrx_embed_fwd_train(const nrx_feature_t* feats, int32_t n_feats, 
     for (int i = 0; i < NRX_MAX_FEATURES; ++i) rest_id[i] = (uint8_t)i;
     if (single || per_width) {
         for (int g = 0; g < n_dims; ++g) {
-            const int D0 = dims_seen[g], Q0 = D0 / 4;
+            const int K0 = dims_seen[g], D0 = K0 >> 1, Q0 = D0 / 4;
+            const bool bf16 = (K0 & 1) != 0;
             UniformArgs ua;
             int n = 0;
             bool unal = !out_al;
             for (int i = 0; i < n_feats; ++i)
-                if (el[i] && feats[i].dim == D0) unal |= (feats[i].out_col & 3) != 0;
+                if (el[i] && group_key(feats[i]) == K0) unal |= (feats[i].out_col & 3) != 0;
             for (int i = 0; i < n_feats; ++i) {
-                if (!el[i] || feats[i].dim != D0) continue;
+                if (!el[i] || group_key(feats[i]) != K0) continue;
                 NRX_REQUIRE(feats[i].index != nullptr, "nrx_embed_fwd: feature %d: null index pointer", i);
                 NRX_REQUIRE(feats[i].rows <= 0x7fffffffLL, "nrx_embed_fwd: feature %d: rows out of range", i);
                 ua.table[n] = feats[i].table;
@@ -2547,7 +2673,7 @@ extern "C" int nrx_embed_fwd_train(const nrx_feature_t* feats, int32_t n_feats, 
                 // (tools/ab_stnt.py; NRX_FWD_STNT=0|1 overrides)
                 bool lines = D0 >= 32 && !unal && out != nullptr && (reinterpret_cast<uintptr_t>(out) & 127u) == 0 && (out_ld & 31) == 0;
                 for (int i = 0; i < n_feats && lines; ++i)
-                    if (el[i] && feats[i].dim == D0) lines = (feats[i].out_col & 31) == 0;
+                    if (el[i] && group_key(feats[i]) == K0) lines = (feats[i].out_col & 31) == 0;
                 const char* e = getenv("NRX_FWD_STNT");
                 ua.stnt = e ? atoi(e) : (lines ? 1 : 0);
             }
@@ -2559,12 +2685,22 @@ extern "C" int nrx_embed_fwd_train(const nrx_feature_t* feats, int32_t n_feats, 
             ua.idx64 = feats[0].index_bits == 64;
             const bool fm = fm_out != nullptr && n_fm > 0;
             const bool store = out != nullptr;
-            switch (Q0) {
-                case 4: launch_uniform<2>(ua, batch, fm, store, st); break;
-                case 8: launch_uniform<3>(ua, batch, fm, store, st); break;
-                case 16: launch_uniform<4>(ua, batch, fm, store, st); break;
-                case 32: launch_uniform<5>(ua, batch, fm, store, st); break;
-                default: launch_uniform<6>(ua, batch, fm, store, st); break;
+            if (bf16) {
+                switch (Q0) {
+                    case 4: launch_uniform<2, uint16_t>(ua, batch, fm, store, st); break;
+                    case 8: launch_uniform<3, uint16_t>(ua, batch, fm, store, st); break;
+                    case 16: launch_uniform<4, uint16_t>(ua, batch, fm, store, st); break;
+                    case 32: launch_uniform<5, uint16_t>(ua, batch, fm, store, st); break;
+                    default: launch_uniform<6, uint16_t>(ua, batch, fm, store, st); break;
+                }
+            } else {
+                switch (Q0) {
+                    case 4: launch_uniform<2>(ua, batch, fm, store, st); break;
+                    case 8: launch_uniform<3>(ua, batch, fm, store, st); break;
+                    case 16: launch_uniform<4>(ua, batch, fm, store, st); break;
+                    case 32: launch_uniform<5>(ua, batch, fm, store, st); break;
+                    default: launch_uniform<6>(ua, batch, fm, store, st); break;
+                }
             }
         }
         NRX_LAUNCH_CHECK("nrx_embed_fwd(uniform)");
@@ -2587,6 +2723,7 @@ extern "C" int nrx_embed_fwd_train(const nrx_feature_t* feats, int32_t n_feats, 
     int max_dim, max_bag;
     int rc = pack_features(feats, n_feats, a, max_dim, max_bag, "nrx_embed_fwd");
     if (rc != NRX_OK) return rc;
+    const bool hb = mark_bf16_tables(feats, n_feats, a);
     for (int i = 0; i < NRX_MAX_FEATURES; ++i) a.feat_id[i] = rest_id[i];
     a.batch = batch;
     a.out = out;
@@ -2608,7 +2745,8 @@ extern "C" int nrx_embed_fwd_train(const nrx_feature_t* feats, int32_t n_feats, 
     plan_generic(max_dim, max_bag, qlog2, a.lds_chunk, smem);
     const int tb = NRX_BLOCK >> qlog2;
     const unsigned grid = (unsigned)((batch + tb - 1) / tb);
-    NRX_QSWITCH(qlog2, { hipLaunchKernelGGL((embed_fwd_generic<QL>), dim3(grid), dim3(NRX_BLOCK), smem, st, a); });
+    if (hb) NRX_QSWITCH(qlog2, { hipLaunchKernelGGL((embed_fwd_generic<QL, true>), dim3(grid), dim3(NRX_BLOCK), smem, st, a); })
+    else NRX_QSWITCH(qlog2, { hipLaunchKernelGGL((embed_fwd_generic<QL, false>), dim3(grid), dim3(NRX_BLOCK), smem, st, a); })
     NRX_LAUNCH_CHECK("nrx_embed_fwd(generic)");
     return NRX_OK;
 }

@@ -22,7 +22,7 @@
 #include "nrx_common.h"
 
 struct UniformArgs {
-    const float* table[NRX_MAX_FEATURES];
+    const float* table[NRX_MAX_FEATURES];   // fp32 rows, or bf16 rows (uint16) in the TS = uint16_t launches
     const void* index[NRX_MAX_FEATURES];
     int64_t rows[NRX_MAX_FEATURES];
     int32_t col4[NRX_MAX_FEATURES];   // out column / 4
@@ -83,11 +83,20 @@ __device__ __forceinline__ float group_sum(float v) {
 
 namespace nrx_ring {
 
-template <int QLOG2, bool NT>
+// TS = the table's storage: float, or uint16_t for bf16 tables (NRX_FEAT_TABLE_BF16) -- a lane then loads its 4 columns as 8 bytes and
+// widens them in registers (exact: the fp32 value is the bf16 pattern shifted into the high half).
+typedef unsigned nrx_u32x2 __attribute__((ext_vector_type(2)));
+template <int QLOG2, bool NT, typename TS = float>
 __device__ __forceinline__ float4 load_row(const float* table /*wave-uniform*/, int32_t id, int q) {
-    const NRX_GLOBAL nrx_f32x4* p = (const NRX_GLOBAL nrx_f32x4*)table + (((int64_t)id << QLOG2) + q);
-    const nrx_f32x4 t = NT ? __builtin_nontemporal_load(p) : *p;
-    return make_float4(t.x, t.y, t.z, t.w);
+    if constexpr (sizeof(TS) == 2) {
+        const NRX_GLOBAL nrx_u32x2* p = (const NRX_GLOBAL nrx_u32x2*)table + (((int64_t)id << QLOG2) + q);
+        const nrx_u32x2 t = NT ? __builtin_nontemporal_load(p) : *p;
+        return nrx_bf16x4_to_f32(t.x, t.y);
+    } else {
+        const NRX_GLOBAL nrx_f32x4* p = (const NRX_GLOBAL nrx_f32x4*)table + (((int64_t)id << QLOG2) + q);
+        const nrx_f32x4 t = NT ? __builtin_nontemporal_load(p) : *p;
+        return make_float4(t.x, t.y, t.z, t.w);
+    }
 }
 
 // One step of the walk: hand the finished row of feature f to its consumers.
@@ -136,8 +145,8 @@ __device__ __forceinline__ void stage_ids(const NRX_CONST A* a, int32_t* s_ids, 
 
 }  // namespace nrx_ring
 
-// Requires n >= R (the host sends smaller feature counts to a smaller R).  Dynamic LDS: n * TB * 4 bytes.
-template <int QLOG2, int R, bool FM, bool STORE, bool NT, int MINW = 4>
+// Requires n >= R (the host sends smaller feature counts to a smaller R).  Dynamic LDS: n * TB * 4 bytes.  TS: table storage (load_row).
+template <int QLOG2, int R, bool FM, bool STORE, bool NT, int MINW = 4, typename TS = float>
 __global__ __launch_bounds__(NRX_BLOCK, MINW) void embed_fwd_ring(const UniformArgs args_in_kernarg_segment) {
     using namespace nrx_ring;
     const NRX_CONST UniformArgs* a = nrx_kernarg<UniformArgs>();   // == &args_in_kernarg_segment
@@ -177,7 +186,7 @@ __global__ __launch_bounds__(NRX_BLOCK, MINW) void embed_fwd_ring(const UniformA
 #pragma unroll
         for (int u = 0; u < R; ++u) idn[u] = s_my[u * TB];
 #pragma unroll
-        for (int u = 0; u < R; ++u) v[u] = load_row<QLOG2, NT>(a->table[u], idn[u], q);
+        for (int u = 0; u < R; ++u) v[u] = load_row<QLOG2, NT, TS>(a->table[u], idn[u], q);
     }
     int f0 = 0;
     for (; f0 + 2 * R <= n; f0 += R) {
@@ -187,7 +196,7 @@ __global__ __launch_bounds__(NRX_BLOCK, MINW) void embed_fwd_ring(const UniformA
 #pragma unroll
         for (int u = 0; u < R; ++u) {
             consume<Q, FM, STORE>(a, f0 + u, v[u], q, row4, fm_first, fm_s, fm_q);
-            v[u] = load_row<QLOG2, NT>(a->table[f0 + R + u], idn[u], q);
+            v[u] = load_row<QLOG2, NT, TS>(a->table[f0 + R + u], idn[u], q);
         }
     }
     // f0 + R <= n < f0 + 2R: drain the ring; the n - f0 - R loads still to be issued sit behind wave-uniform branches
@@ -201,7 +210,7 @@ __global__ __launch_bounds__(NRX_BLOCK, MINW) void embed_fwd_ring(const UniformA
 #pragma unroll
         for (int u = 0; u < R; ++u) {
             consume<Q, FM, STORE>(a, f0 + u, v[u], q, row4, fm_first, fm_s, fm_q);
-            if (f0 + R + u < n) v[u] = load_row<QLOG2, NT>(a->table[f0 + R + u], idn[u], q);
+            if (f0 + R + u < n) v[u] = load_row<QLOG2, NT, TS>(a->table[f0 + R + u], idn[u], q);
         }
 #pragma unroll
         for (int u = 0; u < R; ++u)

@@ -278,7 +278,7 @@ bool nrx_launch_uniform_wide(const nrx_feature_t* feats, int32_t n_feats, int64_
     bool any_wide = false;
     for (int i = 0; i < n_feats; ++i) {
         const nrx_feature_t& s = feats[i];
-        if (s.kind != NRX_SPARSE || s.dim != D0 || s.fm_field != 0 || s.index_bits != feats[0].index_bits || s.table == nullptr ||
+        if (s.kind != NRX_SPARSE || s.dim != D0 || s.fm_field != 0 || (s.flags & NRX_FEAT_TABLE_BF16) || s.index_bits != feats[0].index_bits || s.table == nullptr ||
             s.index == nullptr || !nrx_aligned16(s.table) || s.rows < 1 || s.rows > 0x7fffffffLL || s.out_col < 0)
             return false;
         ua.table[i] = s.table;

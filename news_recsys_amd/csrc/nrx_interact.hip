@@ -1245,6 +1245,7 @@ extern "C" int nrx_embed_dcn_v1_fwd(const nrx_feature_t* feats, int32_t n_feats,
     for (int i = 0; i < n_feats; ++i) {
         const nrx_feature_t& s = feats[i];
         NRX_UNSUP(s.kind == NRX_SPARSE && s.wide_col < 0, "nrx_embed_dcn_v1_fwd: feature %d: only plain single-valued features are fused", i);
+        NRX_UNSUP(!(s.flags & NRX_FEAT_TABLE_BF16), "nrx_embed_dcn_v1_fwd: feature %d: bf16 tables are not fused", i);
         NRX_UNSUP((s.dim & 3) == 0 && (s.out_col & 3) == 0 && nrx_aligned16(s.table), "nrx_embed_dcn_v1_fwd: feature %d: dim/out_col %% 4 and 16-byte aligned table required", i);
         NRX_REQUIRE(s.table && s.index && s.rows >= 1 && s.rows <= 0x7fffffffLL, "nrx_embed_dcn_v1_fwd: feature %d: bad table/index/rows", i);
         NRX_REQUIRE(s.index_bits == feats[0].index_bits && (s.index_bits == 32 || s.index_bits == 64), "nrx_embed_dcn_v1_fwd: mixed index widths");

@@ -2092,6 +2092,111 @@ __global__ __launch_bounds__(NRX_BLOCK) void sparse_adam_kernel(const SparseAdam
     }
 }
 
+// bf16 tables (nrx_sparse_adam_step_bf16): the stored weight is widened, adam_elem runs unchanged on fp32 moments, and the new weight is
+// rounded to bf16 stochastically with 16 bits of a stateless counter hash of (seed, step, table, row, column) -- the definition is in
+// nrx_embed.h.  Same lane mapping as sparse_adam_kernel; VEC: dim % 4 == 0, 8-byte aligned bf16 rows and 16-byte aligned moments.
+struct SparseAdamBf16Args {
+    SparseAdamArgs base;        // table[] holds the uint16 tables
+    uint64_t seed;
+    int64_t step;
+    const int64_t* step_dev;    // optional: step read on the device (captured loops)
+};
+static_assert(sizeof(SparseAdamBf16Args) <= 3584, "kernarg budget");
+
+__device__ __forceinline__ uint64_t sr_mix(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ uint16_t sr_bf16(float w, uint64_t h_row, int64_t col) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, w);
+    if ((u & 0x7F800000u) == 0x7F800000u) return __builtin_bit_cast(uint16_t, static_cast<__bf16>(w));   // inf / NaN: plain cast
+    const uint32_t r = (uint32_t)(sr_mix(h_row ^ (uint64_t)col) >> 48);
+    return (uint16_t)((u + r) >> 16);
+}
+
+template <int QLOG2, bool VEC>
+__global__ __launch_bounds__(NRX_BLOCK) void sparse_adam_bf16_kernel(const SparseAdamBf16Args args_in_kernarg) {
+    const NRX_CONST SparseAdamBf16Args* ab = nrx_kernarg<SparseAdamBf16Args>();
+    const NRX_CONST SparseAdamArgs* a = &ab->base;
+    constexpr int Q = 1 << QLOG2;
+    constexpr int TB = NRX_BLOCK / Q;
+    constexpr int R = 4;
+    const int q = threadIdx.x & (Q - 1);
+    const int D = a->dim;
+    const float ss = a->step_size_dev != nullptr ? nrx_gconst<float>(a->step_size_dev)[0] : a->step_size;
+    const uint64_t step = ab->step_dev != nullptr ? (uint64_t)nrx_gconst<int64_t>(ab->step_dev)[0] : (uint64_t)ab->step;
+    int64_t n = a->max_n;
+    if (a->n_dev != nullptr) {
+        const int64_t nd = nrx_gconst<int64_t>(a->n_dev)[0];
+        n = nd < n ? nd : n;
+    }
+    const int64_t u0 = ((int64_t)blockIdx.x * TB + (threadIdx.x >> QLOG2)) * R;
+    if (u0 >= n) return;
+    const uint64_t h_step = sr_mix(sr_mix(ab->seed) ^ step);
+    int64_t key[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) key[r] = u0 + r < n ? nrx_gconst<int64_t>(a->keys)[u0 + r] : -1;
+    uint16_t* p[R];
+    float* pm[R];
+    float* pv[R];
+    uint64_t h[R];
+    bool on[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int64_t t = key[r] >> 40, row = key[r] & ((1ll << 40) - 1);
+        on[r] = key[r] >= 0 && row != 0 && t < a->n_tables;
+        const int64_t tc = on[r] ? t : 0, rc = on[r] ? row : 0;
+        p[r] = reinterpret_cast<uint16_t*>(a->table[tc]) + rc * D;
+        pm[r] = a->m[tc] + rc * a->mom_ld[tc];
+        pv[r] = a->v[tc] + rc * a->mom_ld[tc];
+        h[r] = sr_mix(sr_mix(h_step ^ (uint64_t)tc) ^ (uint64_t)rc);
+    }
+    if (VEC) {
+        for (int k = q * 4; k < D; k += 4 * Q) {
+            float4 g[R], m[R], v[R];
+            uint2 wb[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                g[r] = nrx_ldg4(a->grads + (u0 + (on[r] ? r : 0)) * (int64_t)D + k, 0);
+                wb[r] = *reinterpret_cast<const uint2*>(p[r] + k);
+                m[r] = nrx_ldg4(pm[r] + k, 0);
+                v[r] = nrx_ldg4(pv[r] + k, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if (on[r]) {
+                    const float ox = adam_elem(g[r].x, m[r].x, v[r].x, nrx_bf16_to_f32((uint16_t)wb[r].x), ss, a);
+                    const float oy = adam_elem(g[r].y, m[r].y, v[r].y, nrx_bf16_to_f32((uint16_t)(wb[r].x >> 16)), ss, a);
+                    const float oz = adam_elem(g[r].z, m[r].z, v[r].z, nrx_bf16_to_f32((uint16_t)wb[r].y), ss, a);
+                    const float ow = adam_elem(g[r].w, m[r].w, v[r].w, nrx_bf16_to_f32((uint16_t)(wb[r].y >> 16)), ss, a);
+                    nrx_stg4(pm[r] + k, 0, m[r]);
+                    nrx_stg4(pv[r] + k, 0, v[r]);
+                    uint2 o;
+                    o.x = (uint32_t)sr_bf16(ox, h[r], k) | ((uint32_t)sr_bf16(oy, h[r], k + 1) << 16);
+                    o.y = (uint32_t)sr_bf16(oz, h[r], k + 2) | ((uint32_t)sr_bf16(ow, h[r], k + 3) << 16);
+                    *reinterpret_cast<uint2*>(p[r] + k) = o;
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (!on[r]) continue;
+            const float* g = a->grads + (u0 + r) * (int64_t)D;
+            for (int k = q; k < D; k += Q) {
+                float m = pm[r][k], v = pv[r][k];
+                const float o = adam_elem(g[k], m, v, nrx_bf16_to_f32(p[r][k]), ss, a);
+                pm[r][k] = m;
+                pv[r][k] = v;
+                p[r][k] = sr_bf16(o, h[r], k);
+            }
+        }
+    }
+}
+
 // --------------------------------------------------------------------------------------------
 // Unique-row gradients -> dense gradient tables (the DEFAULT backward of the gather: nn.Embedding(sparse=False)'s
 // [rows, dim] .grad, formed from the deterministic sorted reduction instead of float atomics).
@@ -2488,5 +2593,58 @@ extern "C" int nrx_sparse_adam_step(float* const* tables, float* const* exp_avg,
     }
 #undef NRX_SA
     NRX_LAUNCH_CHECK("nrx_sparse_adam_step");
+    return NRX_OK;
+}
+
+extern "C" int nrx_sparse_adam_step_bf16(uint16_t* const* tables, float* const* exp_avg, float* const* exp_avg_sq, int32_t n_tables,
+                                         int32_t dim, const int64_t* uniq_keys, const float* grads, int64_t n_unique,
+                                         const int64_t* n_unique_dev, float step_size, const float* step_size_dev, float beta1,
+                                         float beta2, float eps, float lr_times_weight_decay, uint64_t sr_seed, int64_t step,
+                                         const int64_t* step_dev, void* stream) {
+    NRX_TRACE();
+    NRX_REQUIRE(n_tables >= 1 && n_tables <= NRX_MAX_FEATURES && dim >= 1 && n_unique >= 0, "nrx_sparse_adam_step_bf16: bad argument");
+    if (n_unique == 0) return NRX_OK;
+    NRX_REQUIRE(tables && exp_avg && exp_avg_sq && uniq_keys && grads, "nrx_sparse_adam_step_bf16: null buffer");
+    SparseAdamBf16Args ab;
+    SparseAdamArgs& a = ab.base;
+    for (int t = 0; t < n_tables; ++t) {       // moment layouts as nrx_sparse_adam_step
+        NRX_REQUIRE(tables[t] && exp_avg[t] && exp_avg_sq[t], "nrx_sparse_adam_step_bf16: table %d: null pointer", t);
+        a.table[t] = reinterpret_cast<float*>(tables[t]);
+        a.m[t] = exp_avg[t];
+        a.v[t] = exp_avg_sq[t];
+        a.mom_ld[t] = exp_avg_sq[t] == exp_avg[t] + dim ? 2 * dim : dim;
+    }
+    a.keys = uniq_keys;
+    a.grads = grads;
+    a.n_dev = n_unique_dev;
+    a.max_n = n_unique;
+    a.n_tables = n_tables;
+    a.dim = dim;
+    a.step_size = step_size;
+    a.step_size_dev = step_size_dev;
+    a.one_minus_b1 = 1.0f - beta1;
+    a.one_minus_b2 = 1.0f - beta2;
+    a.eps = eps;
+    a.decay = lr_times_weight_decay;
+    ab.seed = sr_seed;
+    ab.step = step;
+    ab.step_dev = step_dev;
+    int ql = 0;
+    while ((4 << ql) < dim && ql < 6) ++ql;
+    bool vec = (dim & 3) == 0 && nrx_aligned16(grads);
+    for (int t = 0; t < n_tables && vec; ++t)
+        vec = (reinterpret_cast<uintptr_t>(tables[t]) & 7u) == 0 && nrx_aligned16(exp_avg[t]) && nrx_aligned16(exp_avg_sq[t]);
+    const int tb = NRX_BLOCK >> ql;
+    const int64_t groups = (n_unique + 3) / 4;
+    const unsigned grid = (unsigned)((groups + tb - 1) / tb);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define NRX_SA(QL_) if (vec) hipLaunchKernelGGL((sparse_adam_bf16_kernel<QL_, true>), dim3(grid), dim3(NRX_BLOCK), 0, st, ab); \
+                    else hipLaunchKernelGGL((sparse_adam_bf16_kernel<QL_, false>), dim3(grid), dim3(NRX_BLOCK), 0, st, ab)
+    switch (ql) {
+        case 0: NRX_SA(0); break; case 1: NRX_SA(1); break; case 2: NRX_SA(2); break; case 3: NRX_SA(3); break;
+        case 4: NRX_SA(4); break; case 5: NRX_SA(5); break; default: NRX_SA(6); break;
+    }
+#undef NRX_SA
+    NRX_LAUNCH_CHECK("nrx_sparse_adam_step_bf16");
     return NRX_OK;
 }

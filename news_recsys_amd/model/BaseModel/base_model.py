@@ -31,7 +31,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ..._lib import NRX_BAG_MASKED_MEAN, NRX_BAG_MEAN, NRX_DENSE, NRX_FEAT_BAG_CSR, NRX_SPARSE
+from ..._lib import NRX_BAG_MASKED_MEAN, NRX_BAG_MEAN, NRX_DENSE, NRX_FEAT_BAG_CSR, NRX_FEAT_TABLE_BF16, NRX_SPARSE
 from ...config import load_config, to_container
 from ...lightning_shim import LightningModule
 
@@ -95,6 +95,16 @@ class BaseModel(LightningModule):
         self.index_check = str(e.get("index_check", "deferred")).lower()
         if self.index_check not in ("deferred", "sync", "lazy", "off"):
             raise ValueError("embeddings.index_check must be 'deferred', 'sync', 'lazy' or 'off'")
+        # new optional keys: the tables' storage type.  "bf16" halves the bytes every lookup and every table moves; the kernels widen the
+        # rows (outputs stay fp32) and the tables train only through the fused row-sparse optimizer, which rounds the updated rows back
+        # to bf16 stochastically from the seed `sr_seed`
+        self.table_dtype = str(e.get("table_dtype", "fp32")).lower()
+        if self.table_dtype not in ("fp32", "bf16"):
+            raise ValueError("embeddings.table_dtype must be 'fp32' or 'bf16'")
+        if self.table_dtype == "bf16" and self.sparse_grad != "fused":
+            raise ValueError(f"embeddings.table_dtype: bf16 needs embeddings.sparse_grad: fused (got {e.get('sparse_grad', False)!r}): "
+                             "bf16 tables train only through the fused row-sparse optimizer")
+        self.sr_seed = int(e.get("sr_seed", 0))
 
         self.dataset_cfg = self.config.get("dataset", {}) or {}
         self.train_hparams = self.config.get("train_hparams", {}) or {}
@@ -138,6 +148,9 @@ class BaseModel(LightningModule):
             # nn.Embedding is kept as the parameter container (state_dict key, N(0,1) init, zero padding
             # row); its forward() is never used -- lookups go through the HIP kernels.
             tables[emb_fname] = nn.Embedding(size, dim, padding_idx=0)
+            if self.table_dtype == "bf16":
+                # initialised in fp32 exactly as above (same RNG order), rounded to nearest-even table by table: no fp32 copy of every table
+                tables[emb_fname].to(torch.bfloat16)
         return tables
 
     def _init_metrics_state(self) -> None:
@@ -160,7 +173,11 @@ class BaseModel(LightningModule):
         weight = self._table_weight(feature_name)
         D = weight.shape[1]
         flat = feature_value.reshape(-1)
-        plan = ops.EmbedPlan([ops.Slot(feature_name, NRX_SPARSE, 0, D, 0, 0)], out_width=D)
+        bf16 = weight.dtype is torch.bfloat16
+        if bf16 and torch.is_grad_enabled() and weight.requires_grad:
+            raise RuntimeError("get_feature_embedding: bf16 tables have no per-feature backward; call it under torch.no_grad() "
+                               "(the batch path trains them through the fused row-sparse optimizer)")
+        plan = ops.EmbedPlan([ops.Slot(feature_name, NRX_SPARSE, 0, D, 0, 0, flags=NRX_FEAT_TABLE_BF16 if bf16 else 0)], out_width=D)
         out = ops.embed_apply(plan, [weight], [flat], [None], index_check="sync")[0]
         return out.view(*feature_value.shape, D)
 
@@ -210,8 +227,9 @@ class BaseModel(LightningModule):
             wide = n in wide_names
             if wide and kind != NRX_SPARSE:
                 raise ValueError(f"wide feature '{n}' must be a single-valued sparse feature")
+            bf16 = NRX_FEAT_TABLE_BF16 if self.embedding_tables[tname].weight.dtype is torch.bfloat16 else 0
             slots.append(ops.Slot(n, kind, table_names.index(tname), D, abs(L), col, wide_col=wcol if wide else -1,
-                                  fm_field=int(fm), flags=NRX_FEAT_BAG_CSR if L < 0 else 0))
+                                  fm_field=int(fm), flags=(NRX_FEAT_BAG_CSR if L < 0 else 0) | bf16))
             dims.append(D)
             if wide:
                 wcol += 1
@@ -402,7 +420,7 @@ class BaseModel(LightningModule):
                     self._sparse_sink = ops.SparseGradSink()
                 sink = self._sparse_sink
             optimizer = SparseDenseAdam(table_params, [p for p in self.parameters() if id(p) not in ids], lr=hp.lr, fused_sink=sink,
-                                        exact=self.sparse_grad == "exact")
+                                        exact=self.sparse_grad == "exact", sr_seed=self.sr_seed)
         else:
             from ..model_utils.optim import dense_adamw
             optimizer = dense_adamw(self.parameters(), lr=hp.lr, betas=(0.9, 0.999))     # torch.optim.AdamW; its one-pass kernel on the GPU

@@ -36,10 +36,15 @@ class FusedSparseAdam:
     torch.optim.SparseAdam (tested against it) + optional decoupled weight decay on the touched rows.
     A table that received gradients from several backward groups in one step (DSSM's towers share the news
     table) gets them merged first, so the step is still ONE Adam update per row.  Tables are identified by tensor
-    identity; their moments are created (zeros) the first time a table shows up in the sink."""
+    identity; their moments are created (zeros) the first time a table shows up in the sink.
+
+    bf16 tables (torch.bfloat16; all tables of the optimizer then) keep fp32 moments and step through
+    `nrx_sparse_adam_step_bf16`: the fp32 update of the widened row, rounded back to bf16 stochastically with bits that
+    depend on (sr_seed, step, table, row, column) only -- sr_seed and the step count are in state_dict(), so a resumed run
+    continues the same rounding stream.  `table` is the table's position in `params`, which bf16 tables therefore require."""
 
     def __init__(self, sink: "ops.SparseGradSink", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False,
-                 params=None):
+                 params=None, sr_seed=0):
         """capturable=True keeps the step counter and the bias-corrected step size on the device (like
         torch.optim.Adam(capturable=True)) so step() can be captured in a HIP graph (graph.GraphedStep); lr is
         then fixed at capture time.  params (optional): the table tensors in a stable order -- state_dict() then
@@ -56,16 +61,26 @@ class FusedSparseAdam:
         self._identity = {}      # table-list identity -> that map is the identity
         self._maps = []          # per-table slot maps of the two-list merge (made on first use)
         self.pair_merge = True   # two backward groups of one width: merge by marking (False: the sort-based _merge)
+        self.sr_seed = int(sr_seed) & ((1 << 64) - 1)     # stochastic rounding of bf16 tables
+        if self.params is not None and any(t.dtype is torch.bfloat16 for t in self.params):
+            # the rounding hash names a table by its position here: pinned to the params order, so a run resumed from a checkpoint
+            # (whose load registers the tables in that order) hashes every table as the uninterrupted run does
+            for t in self.params:
+                self._register(t)
 
     def _register(self, t: torch.Tensor) -> int:
         i = self._index.get(id(t))
         if i is None:
+            if t.dtype is torch.bfloat16 and (self.params is None or not any(p is t for p in self.params)):
+                # positions by first appearance in the sink would make the rounding stream depend on the batch order of a run
+                raise ValueError("FusedSparseAdam: bf16 tables need params=<the table list>: their positions in it name them in the "
+                                 "stochastic-rounding hash, which a resumed run must reproduce")
             i = len(self.tables)
             self._index[id(t)] = i
             self.tables.append(t)
             # both moments of a row side by side ([rows, 2, D]; exp_avg / exp_avg_sq are its two views): the update is a random
             # read-modify-write of (w, m, v) and every 64-byte access costs a 128-byte fetch -- adjacent, m and v share one
-            mv = torch.zeros((t.shape[0], 2, t.shape[1]), dtype=t.dtype, device=t.device)
+            mv = torch.zeros((t.shape[0], 2, t.shape[1]), dtype=torch.float32 if t.dtype is torch.bfloat16 else t.dtype, device=t.device)
             self.moments.append((mv[:, 0], mv[:, 1]))
         return i
 
@@ -130,7 +145,19 @@ class FusedSparseAdam:
         tp = (C.c_void_p * n)(*[t.data_ptr() for t in self.tables])
         mp = (C.c_void_p * n)(*[m.data_ptr() for m, _ in self.moments])
         vp = (C.c_void_p * n)(*[v.data_ptr() for _, v in self.moments])
+        n_bf16 = sum(t.dtype is torch.bfloat16 for t in self.tables)
+        if 0 < n_bf16 < n:
+            raise NotImplementedError("FusedSparseAdam: bf16 and fp32 tables in one optimizer")
+        # the rounding stream's step index: the host count, or (capturable) the device count a captured loop advances
+        step_dev = self._t_dev.to(torch.int64).reshape(1) if (n_bf16 and self._t_dev is not None) else None
         def adam(keys, vals):
+            if n_bf16:
+                ops.check(lib.nrx_sparse_adam_step_bf16(tp, mp, vp, n, dim, keys.data_ptr(), vals.data_ptr(), keys.numel(), None,
+                                                        step_size, ss_dev.data_ptr() if ss_dev is not None else None, b1, b2, self.eps,
+                                                        self.lr * self.weight_decay, self.sr_seed, self.t,
+                                                        step_dev.data_ptr() if step_dev is not None else None,
+                                                        torch.cuda.current_stream(keys.device).cuda_stream), "nrx_sparse_adam_step_bf16")
+                return
             ops.check(lib.nrx_sparse_adam_step(tp, mp, vp, n, dim, keys.data_ptr(), vals.data_ptr(), keys.numel(), None,
                                                step_size, ss_dev.data_ptr() if ss_dev is not None else None, b1, b2, self.eps,
                                                self.lr * self.weight_decay,
@@ -184,10 +211,13 @@ class FusedSparseAdam:
         for pos, c in getattr(self, "_steps", {}).items():          # (ExactDenseAdamW: a table's own step count)
             key = self._stable_index(self.tables[pos])
             steps[key if key is not None else f"unlisted:{pos}"] = c
-        return {"t": self.t, "t_dev": None if self._t_dev is None else float(self._t_dev.item()), "tables": tables, "steps": steps}
+        return {"t": self.t, "t_dev": None if self._t_dev is None else float(self._t_dev.item()), "tables": tables, "steps": steps,
+                "sr_seed": self.sr_seed}
 
     def load_state_dict(self, sd):
         self.t = int(sd["t"])
+        if "sr_seed" in sd:
+            self.sr_seed = int(sd["sr_seed"])
         self._t_dev = None
         if sd.get("t_dev") is not None and self.capturable and self.params:
             self._t_dev = torch.tensor(sd["t_dev"], dtype=torch.float64, device=self.params[0].device)
@@ -232,6 +262,8 @@ class ExactDenseAdamW(FusedSparseAdam):
     def _register(self, t: torch.Tensor) -> int:
         i = self._index.get(id(t))
         if i is None:
+            if t.dtype is torch.bfloat16:
+                raise TypeError("ExactDenseAdamW: bf16 tables train with FusedSparseAdam (embeddings.sparse_grad: fused)")
             i = len(self.tables)
             self._index[id(t)] = i
             self.tables.append(t)
@@ -303,7 +335,7 @@ class ExactDenseAdamW(FusedSparseAdam):
 
 class SparseDenseAdam(torch.optim.Optimizer):
     def __init__(self, sparse_params, dense_params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, fused_sink=None,
-                 capturable=False, exact=False):
+                 capturable=False, exact=False, sr_seed=0):
         """fused_sink: an ops.SparseGradSink -> the tables are updated by FusedSparseAdam from the sink instead of
         torch.optim.SparseAdam from COO .grad tensors.  exact (with fused_sink): by ExactDenseAdamW -- the reference's dense AdamW over every
         row, weight decay included, fed from the sink."""
@@ -314,8 +346,11 @@ class SparseDenseAdam(torch.optim.Optimizer):
         super().__init__(groups, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         if exact and fused_sink is None:
             raise ValueError("SparseDenseAdam(exact=True) needs fused_sink")
+        if fused_sink is None and any(p.dtype is torch.bfloat16 for p in sparse_params):
+            raise TypeError("SparseDenseAdam: bf16 tables train only with the fused sink (torch.optim.SparseAdam needs COO gradients, "
+                            "which bf16 tables do not form); use embeddings.sparse_grad: fused")
         self._sparse = (ExactDenseAdamW(fused_sink, sparse_params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable) if exact else
-                        FusedSparseAdam(fused_sink, lr=lr, betas=betas, eps=eps, capturable=capturable, params=sparse_params)
+                        FusedSparseAdam(fused_sink, lr=lr, betas=betas, eps=eps, capturable=capturable, params=sparse_params, sr_seed=sr_seed)
                         if fused_sink is not None
                         else torch.optim.SparseAdam(sparse_params, lr=lr, betas=betas, eps=eps))
         self._dense = (torch.optim.AdamW(dense_params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable)

@@ -113,6 +113,9 @@ class DSSM(BaseModel):
     def configure_optimizers(self):
         from ...model_utils.lr_schedule import CosinDecayLR
         hp = self.hparams_
+        if any(e.weight.dtype is torch.bfloat16 for e in self.embedding_tables.values()):
+            raise NotImplementedError("DSSM trains with dense AdamW over every parameter; bf16 tables (embeddings.table_dtype: bf16) "
+                                      "serve its forward, inference and retrieval only")
         from ...model_utils.optim import dense_adamw
         optimizer = dense_adamw(self.parameters(), lr=hp["lr"], betas=(0.9, 0.999))          # torch.optim.AdamW; its one-pass kernel on the GPU
         sched = CosinDecayLR(optimizer, lrs=[hp["lr"], hp["min_lr"]], milestones=list(hp["lr_milestones"]))

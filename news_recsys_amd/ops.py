@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (NRX_BAG_MASKED_MEAN, NRX_BAG_MEAN, NRX_BAG_SUM, NRX_DENSE, NRX_ERR_UNSUPPORTED, NRX_FEAT_BAG_CSR, NRX_PLAN_PAIRS, NRX_PLAN_SPLIT_PADDING, NRX_FEAT_ROW0_IS_DATA, NRX_MAX_FEATURES, NRX_SPARSE,
+from ._lib import (NRX_BAG_MASKED_MEAN, NRX_BAG_MEAN, NRX_BAG_SUM, NRX_DENSE, NRX_ERR_UNSUPPORTED, NRX_FEAT_BAG_CSR, NRX_PLAN_PAIRS, NRX_PLAN_SPLIT_PADDING, NRX_FEAT_ROW0_IS_DATA, NRX_FEAT_TABLE_BF16, NRX_MAX_FEATURES, NRX_SPARSE,
                    NrxFeature, NrxFmGrad, check)
 
 # ------------------------------------------------------------------------------- helpers
@@ -207,6 +207,22 @@ def _f32c(t: torch.Tensor, what: str) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _check_tables(plan, tables) -> None:
+    """Every table a contiguous device tensor, fp32 -- or bf16 (torch.bfloat16), which the slots that read it must say with
+    NRX_FEAT_TABLE_BF16 (the flag travels in Slot.flags; the kernels widen the rows, so outputs stay fp32)."""
+    f32, bf = torch.float32, torch.bfloat16
+    for t in tables:
+        if not (t.is_cuda and (t.dtype is f32 or t.dtype is bf) and t.is_contiguous()):
+            _dev(t, "embedding table")
+            if t.dtype is not f32 and t.dtype is not bf:
+                raise TypeError(f"embedding table: expected float32 or bfloat16, got {t.dtype}")
+            raise ValueError("embedding tables must be contiguous [rows, dim] fp32 or bf16")
+    for s in plan.slots:
+        if s.kind != NRX_DENSE and (tables[s.table].dtype is bf) != bool(s.flags & NRX_FEAT_TABLE_BF16):
+            raise TypeError(f"feature '{s.name}': its table is {tables[s.table].dtype} but the slot "
+                            f"{'lacks' if tables[s.table].dtype is bf else 'sets'} NRX_FEAT_TABLE_BF16")
+
+
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
@@ -333,10 +349,7 @@ def _prep_inputs(plan: EmbedPlan, tables, inputs, weights):
             raise ValueError(f"feature '{s.name}': masked mean needs a mask")
         ins.append(x)
         ws.append(w)
-    for t in tables:
-        if not (t.is_cuda and t.dtype is f32 and t.is_contiguous()):
-            _f32c(t, "embedding table")
-            raise ValueError("embedding tables must be contiguous [rows, dim] fp32")
+    _check_tables(plan, tables)
     return B, ins, ws
 
 
@@ -468,6 +481,9 @@ class _EmbedFn(torch.autograd.Function):
         ctx.sink = sparse_grad if isinstance(sparse_grad, SparseGradSink) else None
         ctx.sparse_grad = bool(sparse_grad)
         ctx.tables = list(tables) if ctx.sink is not None else None
+        if ctx.sink is None and any(t.dtype is torch.bfloat16 and g for t, g in zip(tables, ctx.needs_input_grad[7:])):
+            raise NotImplementedError("bf16 embedding tables train only through the row-sparse sink (sparse_grad=SparseGradSink, "
+                                      "optim.FusedSparseAdam): dense or COO gradients of a bf16 table are not formed")
         if sparse_grad and any(s.flags & NRX_FEAT_ROW0_IS_DATA for s in plan.slots):
             raise NotImplementedError("sparse_grad: the sorted backward treats row 0 of every table as the padding row; "
                                       "a feature flagged NRX_FEAT_ROW0_IS_DATA (routed-row buffers) needs the dense-gradient mode")
@@ -1355,11 +1371,7 @@ class _FastForward:
         self.fwd = self.lib.nrx_embed_fwd_train
 
     def _bind_tables(self, tables):
-        i64 = torch.float32
-        for t in tables:
-            if not (t.is_cuda and t.dtype is i64 and t.is_contiguous()):
-                _f32c(t, "embedding table")
-                raise ValueError("embedding tables must be contiguous [rows, dim] fp32")
+        _check_tables(self.plan, tables)
         ptrs = [t.data_ptr() for t in tables]
         rows = [t.shape[0] for t in tables]
         self.view["table"] = [ptrs[k] if k >= 0 else 0 for k in self.table_of]
@@ -2385,6 +2397,7 @@ def gather_rows_segmented(tables: Sequence[torch.Tensor], seg_start: torch.Tenso
     """Owner-side gather: rows of tables[seg_table[s]] for local_rows[seg_start[s]:seg_start[s+1]].
     defer_check=True returns (rows, status) without reading the status back (the sharded exchange
     checks it collectively after the return all-to-all); status is None when index checks are off."""
+    refuse_bf16_tables(tables, "gather_rows_segmented")
     lib = _lib.load()
     dim = tables[0].shape[1]
     for t in tables:
@@ -2523,7 +2536,14 @@ def unique_inverse(ids: torch.Tensor):
     return uniq[:int(cnt.item())], inv.view(ids.shape)
 
 
+def refuse_bf16_tables(tables, what: str) -> None:
+    """The sharded engine reads and writes fp32 rows only: bf16 tables (embeddings.table_dtype: bf16) are refused, never misread."""
+    if any(t is not None and t.dtype is torch.bfloat16 for t in tables):
+        raise NotImplementedError(f"{what}: bf16 embedding tables are not supported by the sharded engine")
+
+
 def _inbox_common(tables, feat_table):
+    refuse_bf16_tables(tables, "inbox gather / pool")
     dim = tables[0].shape[1]
     for t in tables:
         _f32c(t, "table")

@@ -46,6 +46,8 @@ def make_arena(rows: int, dim: int, rank: int, world: int, device, full: Optiona
     k * world + rank.  `full` (optional): the unsharded table to take the rows from (scatter-on-load); else N(0, 1) rows (nn.Embedding's init,
     base_model.py:164).  arena[0] is zero and stays zero; on rank 0, arena[1] is the global padding row: zero, never looked up (owner id 0
     stands for it), never trained."""
+    if full is not None:
+        ops.refuse_bf16_tables([full], "make_arena")
     n = local_row_count(rows, rank, world)
     a = torch.empty((n + 1, dim), dtype=torch.float32, device=device)
     if full is not None:
@@ -637,6 +639,7 @@ def shard_model_step_(model, rank: int, world: int, group=None, host_staged: boo
     first call, so such a batch raises before anything is applied; later calls are checked every 64th call only -- calls 2..64 of a step, and
     the calls between two checks after that, can apply a backward and optimizer step on dropped lookups before the next check raises.  Call
     check_shard_steps(model) at epoch end and at teardown to surface what the last calls left."""
+    ops.refuse_bf16_tables([e.weight for e in model.embedding_tables.values()], "shard_model_step_")
     import torch.nn as nn
     from .sharding import RowShardedEmbedding, ShardedFeature
     eng = RowShardedEmbedding(rank, world, group, None, slack=slack, host_staged=host_staged, overflow_policy="defer")

@@ -1032,6 +1032,7 @@ def shard_model_(model, rank: int, world: int, group=None, backend=None):
     state_dict keys are unchanged; values are the local shards (use shard_table / unshard_tables to
     convert checkpoints: scatter-on-load / gather-on-save)."""
     import torch.nn as nn
+    ops.refuse_bf16_tables([e.weight for e in model.embedding_tables.values()], "shard_model_")
     if getattr(model, "sparse_grad", False):
         # the routed backward delivers dense shard gradients; the row-sparse optimizers expect COO grads / the fused sink
         raise NotImplementedError("shard_model_: embeddings.sparse_grad is not supported together with row-sharded tables")

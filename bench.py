@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- impressions/sec of the embedding hot path at batch 65536 (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -24,6 +24,12 @@ link, next to the 7 x 153 GB/s of the links); "fwd_bwd" is the bound sharded tra
 owner-side row-sparse reduction) with its own roofline.  The N > 1 line also carries `rccl_ranks` (the process group's own world
 size and backend) and `scaling_vs_1gpu` (value / N over the DIRECT single-GPU path's committed number of the same workload).
 A watchdog prints the headline line if a secondary leg stalls.  Rank 0 prints ONE JSON line.
+
+A plain run does what its headline figure needs and nothing else: it sets up, warms up, times the steps, writes the
+--dump-outputs files and prints the line.  Everything else the line can carry -- the per-step spread, the plain-copy rate
+next to the roofline, the CPU baselines, the N = 1 secondary legs (distinct output buffers, fwd_bwd, module path, input
+pipeline, DCN-v2 cross, wide split), the N > 1 secondary job and `scaling_vs_1gpu` -- runs only with --full, after the
+timed region as before.  --headline-only and --no-cpu-baseline trim a --full run.
 """
 from __future__ import annotations
 
@@ -121,9 +127,9 @@ def run_ranks(n: int, child_cmd: list, timeout_s: float, extra_env: dict | None 
 def self_launch(args, argv: list) -> int:
     """`python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment: be the launcher.  Job 1 runs the N ranks
     with --headline-only (the timed region of the contract and nothing else: a clean, separately exiting measurement);
-    job 2 re-runs them with the secondary legs (other layout, strong scaling, all-to-all probe) and only its secondary
-    fields are merged into job 1's line -- if job 2 fails or stalls it is killed, a note says so, and the exit code stays
-    that of the measurement.  NRX_BENCH_LAUNCH_TIMEOUT (s, default 1500) bounds each job."""
+    with --full, job 2 re-runs them with the secondary legs (other layout, strong scaling, all-to-all probe) and only its
+    secondary fields are merged into job 1's line -- if job 2 fails or stalls it is killed, a note says so, and the exit
+    code stays that of the measurement.  NRX_BENCH_LAUNCH_TIMEOUT (s, default 1500) bounds each job."""
     n = args.gpus
     timeout_s = float(os.environ.get("NRX_BENCH_LAUNCH_TIMEOUT", "1500"))
     me = [sys.executable, os.path.abspath(__file__)]
@@ -141,9 +147,11 @@ def self_launch(args, argv: list) -> int:
             print(ln, flush=True)
         sys.stderr.write(f"bench.py: the {n}-rank headline job failed (rc {rc}){': ' + note if note else ''}\n")
         return rc or 1
+    secondary = args.full and not args.headline_only
     head["launcher"] = (f"self-launched: {n} rank processes started by `python bench.py --gpus {n}` (RANK / LOCAL_RANK / WORLD_SIZE / "
-                        "MASTER_ADDR=127.0.0.1 in their environment), headline job with --headline-only, secondary legs as a second job")
-    if not args.headline_only:
+                        "MASTER_ADDR=127.0.0.1 in their environment), headline job with --headline-only"
+                        + (", secondary legs as a second job" if secondary else ""))
+    if secondary:
         rc2, lines2, note2 = run_ranks(n, me + base, min(timeout_s, args.secondary_timeout + 600.0))
         sec = None
         for ln in lines2:
@@ -172,8 +180,11 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="c2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--headline-only", action="store_true", help="skip the secondary legs (distinct output buffers, fwd+bwd)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure what the headline does not need: per-step spread, plain-copy rate, CPU "
+                         "baselines, secondary legs (N > 1: the secondary job) and the comparison with the committed single-GPU line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--headline-only", action="store_true", help="--full without the secondary legs (distinct output buffers, fwd+bwd, ...)")
     ap.add_argument("--ids", default="uniform", choices=["uniform", "zipf"],
                     help="id distribution: uniform (headline, cache-hostile) or Zipf(1.05) popularity (MIND-like); N=1 only")
     ap.add_argument("--force-sharded", action="store_true", help="run the row-sharded engine even at N=1 (testing)")
@@ -182,7 +193,7 @@ def parse_args(argv=None):
                          "larger ones row-sharded); 'default' = row for every workload.  The other layout is timed "
                          "too (field `other_layout`, which says how many tables it replicated).")
     ap.add_argument("--secondary-timeout", type=float, default=240.0,
-                    help="N>1: seconds the secondary legs (other layout, strong scaling, a2a probe) may take before the "
+                    help="N>1 with --full: seconds the secondary legs (other layout, strong scaling, a2a probe) may take before the "
                          "headline line is printed without them")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the LAST timed step returned (out / wide / fm) as DIR/<name>.npy; above "
@@ -903,6 +914,8 @@ def main():
         # layout for c2 / c3, whose 64 MB tables it replicates -- zero all-to-all: a data-parallel copy would have "scaled" 8x)
         args.shard_mode = "row"
 
+    # a plain run measures the headline and nothing else; --full adds the rest, all of it after the timed region
+    secondary = args.full and not args.headline_only
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -996,9 +1009,9 @@ def main():
     dumped = dump_outputs(last, args.dump_outputs, getattr(path, "out_cols", None)) if args.dump_outputs and rank == 0 else None
     del last
 
-    # per-step spread (outside the timed region, rank 0 / N=1 only): each step bracketed by its own pair of events
+    # per-step spread (--full; outside the timed region, rank 0 / N=1 only): each step bracketed by its own pair of events
     spread = None
-    if world == 1:
+    if world == 1 and args.full:
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(64)]
         for i, (a, b) in enumerate(evs):
             a.record()
@@ -1019,9 +1032,9 @@ def main():
         except Exception:       # noqa: BLE001
             return None
 
-    # what a plain copy sustains on THIS box, same run: 1 GiB read + 1 GiB written per launch, 16 bytes per lane
+    # (--full) what a plain copy sustains on THIS box, same run: 1 GiB read + 1 GiB written per launch, 16 bytes per lane
     stream_copy = None
-    if world == 1 and not args.force_sharded and hasattr(path, "lib"):
+    if world == 1 and args.full and not args.force_sharded and hasattr(path, "lib"):
         try:
             nbytes = 1 << 30
             src = torch.empty(nbytes // 4, dtype=torch.float32, device=device).normal_()
@@ -1041,7 +1054,7 @@ def main():
         except Exception:       # noqa: BLE001
             stream_copy = None
 
-    # secondary legs at N = 1, outside the headline timed region
+    # secondary legs at N = 1 (--full), outside the headline timed region
     distinct = fwd_bwd = wide_split = module_path = dcn_v2_cross = None
     def sharded_train_leg(path):
         # the sharded engine's TRAINING step (every world size, 1 included): forward exchange + gradient all-to-all back to the owners + owner-side
@@ -1120,14 +1133,14 @@ def main():
         return fwd_bwd
 
     input_pipeline = None
-    if world == 1 and not args.force_sharded and not args.headline_only and args.workload == "c2" and hasattr(path, "plan"):
+    if world == 1 and secondary and not args.force_sharded and args.workload == "c2" and hasattr(path, "plan"):
         try:
             input_pipeline = input_pipeline_leg(path)
         except Exception as e:          # noqa: BLE001 -- a secondary leg must not cost the line
             input_pipeline = {"error": f"{type(e).__name__}: {e}"[:300]}
-    if world == 1 and hasattr(path, "train_setup") and not args.headline_only:
+    if world == 1 and secondary and hasattr(path, "train_setup"):
         fwd_bwd = sharded_train_leg(path)        # (N > 1: behind the headline line and the watchdog, with the other secondary legs)
-    if world == 1 and not args.force_sharded and not args.headline_only:
+    if world == 1 and secondary and not args.force_sharded:
         def time_calls(fn, n):
             # warm-up by TIME (>= 50 ms of the same launches): the legs that contain latency-bound launches (the backward's
             # planning) depend on the core clock, which takes tens of milliseconds to come up after an idle gap
@@ -1281,7 +1294,7 @@ def main():
                        "algorithmic_bytes_per_impression": survey_bytes,
                        **({"algorithmic_bytes_per_impression_with_cross_write": bytes_per_impr} if survey_bytes != bytes_per_impr else {}),
                        "algorithmic_bytes_definition": getattr(path, "bytes_note", "SURVEY 8d"), "id_pool": 8,
-                       "output_buffer": "recycled each step (as the caching allocator does); `distinct_output_buffers` has the other mode",
+                       "output_buffer": "recycled each step (as the caching allocator does); `distinct_output_buffers` (--full) has the other mode",
                        "index_check": "on (device status word, read once after the timed region)"},
             "step_us": spread,
             **({"dump_outputs": dumped} if dumped is not None else {}),
@@ -1303,7 +1316,7 @@ def main():
                          "traffic_frac_of_stream_copy": None if (traffic is None or not stream_copy) else traffic / (kern_ms * 1e-3) / 1e9 / stream_copy,
                          "ceiling_note": "granule_bytes_per_launch = the same lookups at the memory system's granules (random row reads in whole 128-byte "
                                          "lines, writes in 64-byte requests); stream_copy_GBps = a plain 1 GiB copy (read + written bytes / time) measured in "
-                                         "this run on this box.  frac can not exceed (algorithmic / granule bytes) x (stream copy / peak); "
+                                         "this run on this box (--full; null otherwise).  frac can not exceed (algorithmic / granule bytes) x (stream copy / peak); "
                                          "traffic_frac_of_stream_copy says how close the launch's REAL traffic rate is to the box's copy rate",
                          "note": "achieved = algorithmic bytes per launch / mean launch duration (HIP events around "
                                  "the timed region on the launch stream / steps); traffic = DRAM bytes per launch from "
@@ -1321,7 +1334,7 @@ def main():
             out["dcn_v2_cross"] = dcn_v2_cross
         if input_pipeline is not None:
             out["input_pipeline"] = input_pipeline
-        if world == 1 and not args.no_cpu_baseline and not args.force_sharded:
+        if world == 1 and args.full and not args.no_cpu_baseline and not args.force_sharded:
             big = sum(t.numel() for t in path.tables) * 4 > (64 << 30)      # host copies of > 64 GB of tables: skip
             if not big:
                 out["cpu_baseline"] = cpu_baseline(path)
@@ -1345,7 +1358,7 @@ def main():
             # what the process group itself reports (not the launcher's environment): the N > 1 line must be able to show that N ranks exchanged
             out["rccl_ranks"] = {"world_size": dist.get_world_size(), "backend": dist.get_backend(),
                                  "transport": "host-staged gloo (NRX_BENCH_HOST_STAGED test transport: NOT a measurement)" if staged else "RCCL over xGMI"}
-            ref = _direct_1gpu_reference(args.workload)
+            ref = _direct_1gpu_reference(args.workload) if args.full else None
             if ref is not None:
                 out["scaling_vs_1gpu"] = {"direct_1gpu_value": ref["value"], "direct_1gpu_source": ref["source"],
                                           "ratio": out["value"] / ref["value"], "per_gpu_efficiency": out["value"] / world / ref["value"],
@@ -1381,7 +1394,7 @@ def main():
         if rank == 0:
             _print_line(note)
 
-    if world > 1 and not args.headline_only:
+    if world > 1 and secondary:
         # secondary legs (never the headline `value`).  None of the multi-rank collectives below could be exercised on real
         # xGMI while this was written: a watchdog prints the headline line and leaves if they stall
         import threading

@@ -69,7 +69,7 @@ def test_plain_python_gpus2_without_gpu_fails_loudly_not_silently():
 def test_bench_gpus2_self_launched_host_staged_end_to_end():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update({"NRX_BENCH_HOST_STAGED": "1", "NRX_BENCH_LAUNCH_TIMEOUT": "900"})
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
                         "--secondary-timeout", "400"], env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     js = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")]
@@ -97,7 +97,7 @@ def test_bench_single_rank_rccl_forced_dist():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update({"NRX_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29517", "RANK": "0", "WORLD_SIZE": "1",
                 "LOCAL_RANK": "0"})
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--force-sharded",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--force-sharded", "--full",
                         "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     js = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")]

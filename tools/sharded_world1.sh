@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT" || exit 2
 F=gpurun_out/sharded_w1; mkdir -p $F
 export NRX_BENCH_OUT=$F/lines.jsonl; : > $NRX_BENCH_OUT
 for w in ${@:-c2 c5 c3 c4}; do
-  python3 bench.py --workload $w --force-sharded --shard-mode row --steps 100 --warmup 10 --no-cpu-baseline > $F/$w.log 2>&1
+  python3 bench.py --full --workload $w --force-sharded --shard-mode row --steps 100 --warmup 10 --no-cpu-baseline > $F/$w.log 2>&1
   python3 - <<PY
 import json
 for l in open("$F/lines.jsonl"):

@@ -833,6 +833,29 @@ NRX_API int nrx_topk_ip(const float* items, int64_t n_items, int32_t dim, const 
 /* lens[b] = #(mask[b,:] != 0); used to build CSR offsets from the reference's padded masks. */
 NRX_API int nrx_mask_lengths(const float* mask, int64_t batch, int32_t bag_len, int64_t* lens, void* stream);
 
+/* ---- replicated tables' gradient in the bound sharded step (shard_step.PreparedShardedStep(replicated_grads=True)) ---------------------
+ * Small tables held in full on every rank: every rank must end a step with the SAME (keys, values) -- the float32 fold over ranks in rank order
+ * s = G_0; s = s + G_1; ...; s = s + G_{W-1} (G_r = rank r's local gradient, dense, +0.0 where it looked nothing up), keys = the union of the
+ * rows the ranks looked up.  A dense reduce-scatter by chunks: nrx_rep_pack -> equal-split all-to-all -> nrx_rep_ordered_sum -> all-gather ->
+ * nrx_rep_compact.  Layout of the buffer: `world` chunks of C = cf + cr 4-byte words (cf, cr multiples of 4); float element i of the flat
+ * gradient (table t's (row, col): i = voff[t] + row * dim[t] + col) lives at word (i / cf) * C + i % cf, the int32 touch count of row
+ * j = roff[t] + row at word (j / cr) * C + cf + j % cr.  Table arrays (voff, roff, rows, dims, key_table) are HOST arrays of <= 64 entries.
+ * nrx_rep_pack: zero-fills buf [world * C] and scatters n_lists (<= 8) local lists -- keys[l] (device int64, (table << 40) | row, table = index
+ *   into the table arrays), values[l] [cap, dims[l]], n_keys[l] (device int64[1]: the valid prefix) -- setting each listed row's count to 1.
+ * nrx_rep_ordered_sum: out[w] = recv[0][w] + recv[1][w] + ... (rank order; int32 sum for the count words) over one chunk: recv [world][C].
+ * nrx_rep_compact: over the gathered buffer full [world][C], the rows of the n_tables ADJACENT tables of one `dim` (roff[t + 1] = roff[t] +
+ *   rows[t]) whose count is > 0, in row order: keys[p] = (key_table[t] << 40) | row, values[p, :dim]; n_out[0] (device) = their number.
+ *   cap >= the tables' rows.  workspace: nrx_rep_compact_workspace(rows) device bytes.
+ * No float atomics, no host reads.  No reference counterpart (the reference is single-device: src/model/sort/deep/train.py:38-44). */
+NRX_API int nrx_rep_pack(const int64_t* const* keys, const float* const* values, const int64_t* const* n_keys, const int64_t* caps,
+                 const int32_t* dims, int32_t n_lists, const int64_t* voff, const int64_t* roff, const int64_t* rows,
+                 const int32_t* tdims, int32_t n_tables, int32_t world, int64_t cf, int64_t cr, float* buf, void* stream);
+NRX_API int nrx_rep_ordered_sum(const float* recv, int32_t world, int64_t cf, int64_t cr, float* out, void* stream);
+NRX_API int64_t nrx_rep_compact_workspace(int64_t n_rows);
+NRX_API int nrx_rep_compact(const float* full, int32_t world, int64_t cf, int64_t cr, const int64_t* voff, const int64_t* roff,
+                    const int64_t* rows, const int32_t* key_table, int32_t n_tables, int32_t dim, int64_t* keys, float* values,
+                    int64_t cap, int64_t* n_out, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

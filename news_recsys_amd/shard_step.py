@@ -60,6 +60,21 @@ def make_arena(rows: int, dim: int, rank: int, world: int, device, full: Optiona
     return a
 
 
+def replicated_layout(tables: Sequence[tuple], world: int) -> dict:
+    """The dense buffer of the replicated tables' gradient exchange (csrc/nrx_replicated.hip) for `tables` = [(rows, dim)] in layout order:
+    float element (t, row, col) has flat index i = voff[t] + row * dim + col, the touch count of row (t, row) index j = roff[t] + row; `world`
+    chunks of C = cf + cr words (cf, cr multiples of 4), element i at word (i // cf) * C + i % cf, count j at word (j // cr) * C + cf + j % cr."""
+    voff, roff, f, r = [], [], 0, 0
+    for rows, dim in tables:
+        voff.append(f)
+        roff.append(r)
+        f += rows * dim
+        r += rows
+    cf = max(4, (-(-f // world) + 3) // 4 * 4)
+    cr = max(4, (-(-r // world) + 3) // 4 * 4)
+    return dict(voff=voff, roff=roff, floats=f, rows=r, cf=cf, cr=cr, C=cf + cr)
+
+
 def arena_shard(arena: torch.Tensor) -> torch.Tensor:
     """The legacy view of an arena: [local rows, dim] = global rows rank::world (what shard_table / the checkpoints use)."""
     return arena[1:]
@@ -71,7 +86,8 @@ class PreparedShardedStep:
 
     def __init__(self, eng: RowShardedEmbedding, feats: Sequence[ShardedFeature], inputs, weights, arenas: Dict[str, torch.Tensor],
                  out_ld: Optional[int] = None, out: Optional[torch.Tensor] = None, fm: Optional[torch.Tensor] = None, train: bool = True,
-                 slack: Optional[float] = None, one_sided: Optional[bool] = None, binary_masks: bool = False, check_index: bool = False):
+                 slack: Optional[float] = None, one_sided: Optional[bool] = None, binary_masks: bool = False, check_index: bool = False,
+                 replicated_grads: bool = False):
         """one_sided (default: NRX_SHARD_ONE_SIDED = 1 | 0, else on for plans without an FM epilogue): ONE-SIDED PLACEMENT of the forward -- the
         sample positions travel with the owner ids and the owner's gather (nrx_gather_place_feat) writes every row straight into its place in the
         requester's concat, which every rank maps once (hipIpc through torch's CUDA-IPC sharing; over xGMI a peer mapping): no row buffer, no
@@ -81,12 +97,23 @@ class PreparedShardedStep:
         src/dataset/DataReader/data_reader.py:96-109; always true for mean pooling): the pooled channel's backward then never expands the owner's
         entries into rows -- the requester sends the sample gradients pre-multiplied by the sample's weight, the owner's plan lists those rows
         directly (nrx_sparse_plan_ex with NRX_PLAN_PAYLOAD) and the walk reads a [world * n * B, dim] block that stays in the L2 (the single-GPU bag backward's
-        form).  False (default): the general form (nrx_pool_inbox_expand: any weights)."""
+        form).  False (default): the general form (nrx_pool_inbox_expand: any weights).
+        replicated_grads: the backward also covers the REPLICATED features (ShardedFeature.replicated: tables held in full on every rank, read by the
+        final launch with the original ids) -- backward() returns their entries next to the exchange groups' (see _bind_replicated); off (default):
+        those tables get no gradient.  Only replicated features may be wide (Wide&Deep's column routing stays local to the final launch)."""
         import os
         self.lib = _lib.load()
         self.eng = eng
         self.feats = list(feats)
         self.binary_masks = bool(binary_masks)
+        self.replicated_grads = bool(replicated_grads)
+        for f in feats:
+            if f.wide and f.kind != NRX_DENSE and not f.replicated:
+                raise NotImplementedError(f"PreparedShardedStep: wide feature '{f.name}' is row-sharded; the wide column routing is bound for "
+                                          "replicated tables only -- replicate its table (ShardedFeature.replicated / shard_model_step_(replicate=...))")
+        self.rep_idx = [i for i, f in enumerate(feats) if f.kind != NRX_DENSE and f.replicated]
+        self.rep_names = eng.replicated_tables(feats)
+        self.rep = None
         # check_index: the owners' launches record lookups that cannot be rows of their shard (an id outside its table: the reference's nn.Embedding
         # raises IndexError on the CPU, src/model/BaseModel/base_model.py:271) in a device status word; check() reads it, agrees over the ranks and raises
         self.status = torch.zeros(4, dtype=torch.int32, device=inputs[0].device) if check_index else None
@@ -104,6 +131,7 @@ class PreparedShardedStep:
         plan = eng._final_plan(feats, groups, pooled)
         B0 = inputs[0].shape[0]
         dev0 = inputs[0].device
+        self.dev0 = dev0
         ld0 = int(out_ld) if out_ld else plan.out_width
         if one_sided is None:
             env = os.environ.get("NRX_SHARD_ONE_SIDED")
@@ -223,8 +251,16 @@ class PreparedShardedStep:
         self.single = len(feats) <= ops.NRX_MAX_FEATURES
         self.ld = ld0
         self.fm_pass = None
+        # check_index: the final launch records out-of-range ids of the replicated features (it reads their tables with the original ids);
+        # check() names the first such feature (a routed feature's slot of -1 -- a dropped lookup -- is the overflow check's business)
+        final_check = check_index and bool(self.rep_idx)
+        final_feats = [i for i in range(len(feats)) if i not in placed_feats]
+        self._final_rep_flag = None
+        if final_check:
+            self._final_rep_flag = torch.tensor([i + 1 if feats[i].replicated else 0 for i in final_feats], dtype=torch.int64, device=dev0)
         if not placed_feats:
-            self.final = ops.PreparedEmbed(plan, rets, final_inputs, final_weights, out_ld=out_ld, out=out, fm=fm, fm_sums=self.fm_sums)
+            self.final = ops.PreparedEmbed(plan, rets, final_inputs, final_weights, out_ld=out_ld, out=out, fm=fm, fm_sums=self.fm_sums,
+                                           check_index=final_check)
             self.out = self.final.out
         else:
             self.out = out
@@ -234,7 +270,8 @@ class PreparedShardedStep:
                 self.fm_pass = (len(feats), feats[0].dim)
             if rest:
                 sp = ops.EmbedPlan([plan.slots[i] for i in rest], out_width=plan.out_width, wide_width=0)
-                self.final = ops.PreparedEmbed(sp, rets, [final_inputs[i] for i in rest], [final_weights[i] for i in rest], out_ld=ld0, out=out)
+                self.final = ops.PreparedEmbed(sp, rets, [final_inputs[i] for i in rest], [final_weights[i] for i in rest], out_ld=ld0, out=out,
+                                               check_index=final_check)
         self.bwd = None
         # where the owner-side plan (it depends on the owner ids only) is enqueued: "inline" = in backward(), behind the gradient exchange;
         # "backward" = on the planning side stream at the start of backward(), next to the pack launch and the gradient all-to-all;
@@ -353,22 +390,31 @@ class PreparedShardedStep:
         optimizer step of it) and then on calls 65, 129, ...: calls 2..64 of a step (and the calls after each check until the next one) can still
         be applied -- backward and optimizer on the truncated lookups -- before an overflow in them surfaces; check_shard_steps(model) covers them
         at epoch end or teardown."""
-        bad = torch.zeros(2, dtype=torch.int64, device=self.groups[0]["dev"] if self.groups else "cpu")
+        bad = torch.zeros(3, dtype=torch.int64, device=self.dev0)
         if self.status is not None:
             bad[0] = self.status[0].to(torch.int64)
+        fst = self.final.status if self.final is not None else None
+        if fst is not None:       # [2] = 1 + index of the replicated feature that first read outside its table (the largest over the ranks)
+            flag = self._final_rep_flag
+            bad[2] = flag[fst[1].to(torch.int64).clamp(0, flag.numel() - 1)] * (fst[0] != 0).to(torch.int64)
         for g in self.groups:
             if not g["pooled"] and not g["placed"] and g["owner_fwd"].status is not None:
                 bad[0] += g["owner_fwd"].status[0].to(torch.int64)
             over = (g["overflow"][0] > (g["cap"] if g["pooled"] else g["capf"])).to(torch.int64)
             bad[1] = torch.maximum(bad[1], over)
         self.eng._all_reduce_max(bad)
-        n_bad, over = bad.tolist()
+        n_bad, over, rep = bad.tolist()
         if self.status is not None:
             self.status.zero_()
+        if fst is not None:
+            fst.zero_()
         for g in self.groups:
             g["overflow"].zero_()
             if not g["pooled"] and not g["placed"] and g["owner_fwd"].status is not None:
                 g["owner_fwd"].status.zero_()
+        if rep:
+            raise IndexError(f"index out of range in self: a lookup of the replicated feature '{self.feats[rep - 1].name}' named a row outside "
+                             "its table on some rank")
         if n_bad:
             raise IndexError("index out of range in self: a routed lookup named a row outside its table on some rank")
         if over:
@@ -384,8 +430,10 @@ class PreparedShardedStep:
         return bad
 
     # ------------------------------------------------------------------ backward
-    def bind_backward(self, g_out: Optional[torch.Tensor], g_fm: Optional[torch.Tensor] = None, direct_grad: Optional[bool] = None):
-        """Bind the upstream gradient buffers (read in place on every backward()): g_out [B, out_ld] of the concat, g_fm [B] of the FM logit.
+    def bind_backward(self, g_out: Optional[torch.Tensor], g_fm: Optional[torch.Tensor] = None, direct_grad: Optional[bool] = None,
+                      g_wide: Optional[torch.Tensor] = None):
+        """Bind the upstream gradient buffers (read in place on every backward()): g_out [B, out_ld] of the concat, g_fm [B] of the FM logit,
+        g_wide [B, wide width] of the wide columns (replicated wide features, replicated_grads=True).
         direct_grad (default: NRX_SHARD_DIRECT_GRAD = 1 | 0, else on where it applies -- exchange groups of 16 / 32 / 64-wide single-valued
         features with aligned columns): THE REQUESTER'S PACK IS THE OWNER'S PLACEMENT PASS.  The owner plans first and its plan's dest[] comes
         back to the requesters (an int32 all-to-all in the ids' layout); a gradient row whose table row is looked up ONCE in the whole exchange
@@ -479,12 +527,90 @@ class PreparedShardedStep:
             g_recv = g_send if W == 1 else torch.empty_like(g_send)
             owner_bwd = ops.PreparedSparseBackward(g["owner_fwd"], g_recv)
             self.bwd.append(dict(pooled=False, direct=False, arr=arr, g_send=g_send, g_recv=g_recv, owner=owner_bwd, scatter_ok=True))
+        self.g_wide = None if g_wide is None else ops._f32c(g_wide, "g_wide")
+        self.rep = self._bind_replicated() if (self.replicated_grads and self.rep_idx) else None
         return self
+
+    def _bind_replicated(self):
+        """The replicated features' backward.  LOCAL part: the direct path's planned reduction (ops.PreparedSparseBackward) over this rank's
+        lookups, on a descriptor of the final launch restricted to those slots (FM term from the final launch's fm_sums and concat, wide columns
+        from g_wide, bags as the final launch pooled them); keys = (index in rep_names << 40) | row.  World 1: those entries as they are.
+        World > 1 (csrc/nrx_replicated.hip): pack every local list into one dense buffer of `world` chunks (+ an int32 touch count per row) ->
+        equal-split all-to-all -> the rank-order sum of the chunk this rank reduces -> all-gather -> per embedding dim the rows some rank looked
+        up, in row order.  Every rank ends with the same keys and bits: s = G_0; s = s + G_1; ... (G_r = rank r's local gradient, +0.0 for
+        rows it did not touch).  Traffic per rank and step: 2 (W - 1) / W of the replicated tables' bytes (+ 4 bytes per row)."""
+        import dataclasses
+        lib, plan, feats, W = self.lib, self.plan, self.feats, self.eng.world
+        inputs, weights, arenas = self.keep
+        names = self.rep_names
+        tables = [arenas[t] for t in names]
+        slots = [dataclasses.replace(plan.slots[i], table=names.index(feats[i].table)) for i in self.rep_idx]
+        sub = ops.EmbedPlan(slots, out_width=plan.out_width, wide_width=plan.wide_width, use_fm=plan.use_fm)
+        fwd = ops.PreparedEmbed(sub, tables, [inputs[i] for i in self.rep_idx], [weights[i] for i in self.rep_idx], out_ld=self.ld,
+                                need_out=False, out=self.out if self.fm_sums is not None else None, fm_sums=self.fm_sums)
+        bwd = ops.PreparedSparseBackward(fwd, self.g_out, g_fm=self.g_fm if self.fmg is not None else None, g_wide=self.g_wide)
+        tids = [sorted(set(og["tof"])) for og in bwd.groups]
+        r = dict(bwd=bwd, tables=tables, tids=tids)
+        if W == 1:
+            return r
+        order = [t for ts in tids for t in ts]              # layout: the tables of one dim side by side (one compaction per dim)
+        lay = replicated_layout([tuple(tables[t].shape) for t in order], W)
+        at = {t: k for k, t in enumerate(order)}
+        n, cf, cr = len(tables), lay["cf"], lay["cr"]
+        G = bwd.groups
+        r.update(lay=lay, n=n,
+                 voff=(C.c_int64 * n)(*[lay["voff"][at[t]] for t in range(n)]), roff=(C.c_int64 * n)(*[lay["roff"][at[t]] for t in range(n)]),
+                 rows=(C.c_int64 * n)(*[tables[t].shape[0] for t in range(n)]), tdims=(C.c_int32 * n)(*[tables[t].shape[1] for t in range(n)]),
+                 pk=(C.c_void_p * len(G))(*[og["uniq"].data_ptr() for og in G]), pv=(C.c_void_p * len(G))(*[og["values"].data_ptr() for og in G]),
+                 pn=(C.c_void_p * len(G))(*[og["counts"].data_ptr() for og in G]), pc=(C.c_int64 * len(G))(*[og["cap"] for og in G]),
+                 pd=(C.c_int32 * len(G))(*[og["dim"] for og in G]),
+                 send=torch.empty(W * (cf + cr), dtype=torch.float32, device=self.dev0),
+                 recv=torch.empty(W * (cf + cr), dtype=torch.float32, device=self.dev0),
+                 red=torch.empty(cf + cr, dtype=torch.float32, device=self.dev0),
+                 full=torch.empty(W * (cf + cr), dtype=torch.float32, device=self.dev0))
+        r["compact"] = []
+        for og, ts in zip(G, tids):
+            cap = sum(tables[t].shape[0] for t in ts)
+            k = len(ts)
+            r["compact"].append(dict(
+                dim=og["dim"], n=k, cap=cap, table_ids=ts,
+                voff=(C.c_int64 * k)(*[lay["voff"][at[t]] for t in ts]), roff=(C.c_int64 * k)(*[lay["roff"][at[t]] for t in ts]),
+                rows=(C.c_int64 * k)(*[tables[t].shape[0] for t in ts]), kt=(C.c_int32 * k)(*ts),
+                keys=torch.zeros(max(cap, 1), dtype=torch.int64, device=self.dev0),
+                values=torch.zeros((max(cap, 1), og["dim"]), dtype=torch.float32, device=self.dev0),
+                counts=torch.zeros(2, dtype=torch.int64, device=self.dev0),
+                ws=torch.empty(max(8, lib.nrx_rep_compact_workspace(cap)), dtype=torch.uint8, device=self.dev0)))
+        return r
+
+    def _replicated_backward(self):
+        r = self.rep
+        groups = r["bwd"].run()
+        W = self.eng.world
+        if W == 1:
+            return [dict(tables=r["tables"], dim=og["dim"], uniq=og["uniq"], values=og["values"], counts=og["counts"], cap=og["cap"],
+                         table_ids=list(ts)) for og, ts in zip(groups, r["tids"])]
+        lib, eng = self.lib, self.eng
+        stream = torch.cuda.current_stream(self.dev0).cuda_stream
+        cf, cr = r["lay"]["cf"], r["lay"]["cr"]
+        ops.check(lib.nrx_rep_pack(r["pk"], r["pv"], r["pn"], r["pc"], r["pd"], len(groups), r["voff"], r["roff"], r["rows"], r["tdims"], r["n"],
+                                   W, cf, cr, r["send"].data_ptr(), stream), "nrx_rep_pack")
+        eng._a2a(r["recv"], r["send"])
+        ops.check(lib.nrx_rep_ordered_sum(r["recv"].data_ptr(), W, cf, cr, r["red"].data_ptr(), stream), "nrx_rep_ordered_sum")
+        eng._all_gather(r["full"], r["red"])
+        out = []
+        for c in r["compact"]:
+            ops.check(lib.nrx_rep_compact(r["full"].data_ptr(), W, cf, cr, c["voff"], c["roff"], c["rows"], c["kt"], c["n"], c["dim"],
+                                          c["keys"].data_ptr(), c["values"].data_ptr(), c["cap"], c["counts"].data_ptr(), c["ws"].data_ptr(),
+                                          stream), "nrx_rep_compact")
+            out.append(dict(tables=r["tables"], dim=c["dim"], uniq=c["keys"], values=c["values"], counts=c["counts"], cap=c["cap"],
+                            table_ids=list(c["table_ids"])))
+        return out
 
     def backward(self):
         """Enqueue the gradient exchange and the owner-side reduction.  Returns one entry per exchange group in ops.SparseGradSink's format --
         dict(tables (the arenas, index = table id in the keys), dim, uniq [cap] int64 keys table << 40 | arena row, values [cap, dim], counts,
-        cap) -- valid until the next backward(); feed them to optim.FusedSparseAdam through `sink_entries`."""
+        cap) -- valid until the next backward(); feed them to optim.FusedSparseAdam through `sink_entries`.  With replicated_grads, one entry
+        per embedding dim of the replicated features follows (tables = the full replicated tables, keys table << 40 | row; equal on every rank)."""
         lib, eng = self.lib, self.eng
         W = eng.world
         if self.plan_mode == "backward":
@@ -571,7 +697,8 @@ class PreparedShardedStep:
                                 table_ids=list(range(len(g["tables"])))))
 
         self._each_group(one, "bwd")
-        return [e for o in outs for e in o]
+        rep = self._replicated_backward() if self.rep is not None else []
+        return [e for o in outs for e in o] + rep
 
     def sink_entries(self, sink: "ops.SparseGradSink"):
         """backward() into a SparseGradSink (what optim.FusedSparseAdam drains)."""
@@ -585,47 +712,74 @@ class _ShardedStepFn(torch.autograd.Function):
     go to the model's SparseGradSink (what optim.FusedSparseAdam drains) -- the tables never see a dense .grad."""
 
     @staticmethod
-    def forward(ctx, step, sink, scale, want_out, want_fm, anchor):
-        out, _, fm = step.run()
+    def forward(ctx, step, sink, scale, want_out, want_fm, anchor, want_wide=False):
+        out, wide, fm = step.run()
         ctx.step, ctx.sink, ctx.scale = step, sink, scale
         ctx.set_materialize_grads(False)
-        return (out if want_out else None), (fm if want_fm else None)
+        return (out if want_out else None), (wide if want_wide else None), (fm if want_fm else None)
 
     @staticmethod
-    def backward(ctx, g_out, g_fm):
+    def backward(ctx, g_out, g_wide, g_fm):
         step = ctx.step
-        if g_out is None and g_fm is None:
-            return None, None, None, None, None, None
+        if g_out is None and g_fm is None and g_wide is None:
+            return None, None, None, None, None, None, None
         if ctx.scale != 1.0:           # every rank's loss is a mean over ITS batch: the tables see the gradient of the global-batch mean
             g_out = None if g_out is None else g_out * ctx.scale
             g_fm = None if g_fm is None else g_fm * ctx.scale
-        step.set_upstream(g_out, g_fm)
+            g_wide = None if g_wide is None else g_wide * ctx.scale
+        step.set_upstream(g_out, g_fm, g_wide)
         ctx.sink.pending.extend(step.backward())
-        return None, None, None, None, None, None
+        return None, None, None, None, None, None, None
 
 
-def _set_upstream(self, g_out, g_fm):
+def _set_upstream(self, g_out, g_fm, g_wide=None):
     """(Re)bind the upstream gradients of the next backward(): the first call allocates the exchange and plan buffers (bind_backward), later
     calls only swap the pointers the pack launch reads."""
     g_out = None if g_out is None else ops._f32c(g_out, "g_out")
     g_fm = None if g_fm is None else ops._f32c(g_fm, "g_fm")
+    g_wide = None if g_wide is None else ops._f32c(g_wide, "g_wide")
     if self.bwd is None:
-        self.bind_backward(g_out, g_fm)
-        self._had = (g_out is not None, g_fm is not None)
+        self.bind_backward(g_out, g_fm, g_wide=g_wide)
+        self._had = (g_out is not None, g_fm is not None, g_wide is not None)
         return
-    if (g_out is not None, g_fm is not None) != self._had:
+    if (g_out is not None, g_fm is not None, g_wide is not None) != self._had:
         raise RuntimeError("PreparedShardedStep: the set of upstream gradients changed between steps (bind a step per loss form)")
     self.g_out = g_out
+    self.g_wide = g_wide
     if g_fm is not None:
         self.g_fm = g_fm
         self.fmg = NrxFmGrad(g_fm.data_ptr(), self.fm_sums.data_ptr(), self.fm_sums.shape[1], self.out.data_ptr(), self.ld)
+    if self.rep is not None:          # the replicated features' reduction reads the same upstream buffers
+        b = self.rep["bwd"]
+        b.g_out, b.g_wide = g_out, g_wide
+        if g_fm is not None:
+            b.g_fm = g_fm
+            b.fmg = NrxFmGrad(g_fm.data_ptr(), b.fwd.fm_sums.data_ptr(), b.fwd.fm_sums.shape[1], b.fwd.out.data_ptr(), b.fwd.ld)
 
 
 PreparedShardedStep.set_upstream = _set_upstream
 
 
+def replicated_table_names(model, replicate: Sequence[str] = (), replicate_below_bytes: int = 0) -> List[str]:
+    """The tables shard_model_step_ keeps in full on every rank: those named in `replicate` (a table name, or a feature name -- the features
+    that share its table follow it) and those of rows * dim * 4 <= replicate_below_bytes bytes.  In the model's table order."""
+    want = set()
+    for n in replicate:
+        t = n if n in model.embedding_tables else model._get_emb_feature_name(n)
+        if t not in model.embedding_tables:
+            raise ValueError(f"shard_model_step_: replicate={n!r} names no embedding table of the model")
+        want.add(t)
+    out = []
+    for name, emb in model.embedding_tables.items():
+        w = emb.weight
+        if name in want or (replicate_below_bytes > 0 and w.shape[0] * w.shape[1] * 4 <= replicate_below_bytes):
+            out.append(name)
+    return out
+
+
 def shard_model_step_(model, rank: int, world: int, group=None, host_staged: bool = False, slack: float = 0.05, binary_masks: bool = True,
-                      one_sided: Optional[bool] = None, direct_grad: Optional[bool] = None, grad_average: bool = True):
+                      one_sided: Optional[bool] = None, direct_grad: Optional[bool] = None, grad_average: bool = True,
+                      replicate: Sequence[str] = (), replicate_below_bytes: int = 0):
     """Convert a BaseModel in place to row-sharded tables TRAINED BY THE BOUND STEP (the counterpart of sharding.shard_model_, whose backward
     forms dense shard gradients): every `embedding_tables[name].weight` becomes this rank's ARENA ([1 + local rows, D]: row 0 the dummy row,
     rows 1.. = global rows rank::world), `_embed` runs a PreparedShardedStep bound per (feature set, batch size) -- the batch's ids are copied into
@@ -638,7 +792,11 @@ def shard_model_step_(model, rank: int, world: int, group=None, host_staged: boo
     Overflow and out-of-range ids: a bound step is checked (PreparedShardedStep.check, on every rank together) right after the forward of its
     first call, so such a batch raises before anything is applied; later calls are checked every 64th call only -- calls 2..64 of a step, and
     the calls between two checks after that, can apply a backward and optimizer step on dropped lookups before the next check raises.  Call
-    check_shard_steps(model) at epoch end and at teardown to surface what the last calls left."""
+    check_shard_steps(model) at epoch end and at teardown to surface what the last calls left.
+    replicate / replicate_below_bytes (replicated_table_names): tables kept in FULL on every rank ([rows, D], requires_grad False, made equal to
+    rank 0's at conversion, listed in model._replicated_tables): their features read them locally (no exchange) and the bound step reduces
+    their row-sparse gradient over the ranks in rank order (PreparedShardedStep(replicated_grads=True)); FusedSparseAdam updates them from
+    the sink like the arenas.  Wide features (Wide&Deep) must be replicated.  Defaults: every table row-sharded."""
     ops.refuse_bf16_tables([e.weight for e in model.embedding_tables.values()], "shard_model_step_")
     import torch.nn as nn
     from .sharding import RowShardedEmbedding, ShardedFeature
@@ -646,9 +804,16 @@ def shard_model_step_(model, rank: int, world: int, group=None, host_staged: boo
     model.sparse_grad = "fused"
     if getattr(model, "_sparse_sink", None) is None:
         model._sparse_sink = ops.SparseGradSink()
-    model._replicated_tables = ()
+    rep_tables = replicated_table_names(model, replicate, replicate_below_bytes)
+    model._replicated_tables = tuple(rep_tables)
     for name, emb in list(model.embedding_tables.items()):
         w = emb.weight.data
+        if name in rep_tables:
+            full = eng._broadcast(w.detach().clone().contiguous())
+            new = nn.Embedding(full.shape[0], full.shape[1])
+            new.weight = nn.Parameter(full, requires_grad=False)   # (updated in place by FusedSparseAdam from the sink, never through .grad)
+            model.embedding_tables[name] = new
+            continue
         arena = make_arena(emb.num_embeddings, w.shape[1], rank, world, w.device, full=w)
         new = nn.Embedding(arena.shape[0], arena.shape[1])
         new.weight = nn.Parameter(arena, requires_grad=False)      # (updated in place by FusedSparseAdam from the sink, never through .grad)
@@ -663,23 +828,23 @@ def shard_model_step_(model, rank: int, world: int, group=None, host_staged: boo
         plan, table_names, dims, present = model._plan(batch, feature_names, fm, wide_names)
         if not present:
             return None, None, None, [], []
-        if wide_names:
-            raise NotImplementedError("shard_model_step_: Wide&Deep column routing is not bound (sharding.shard_model_ serves it)")
         if out_ld is not None and out_ld < 0:
             out_ld = None
         names = [s.name for s in plan.slots]
         masks = [f"{s.name}_mask" if s.kind == ops.NRX_BAG_MASKED_MEAN else None for s in plan.slots]
         B = batch[names[0]].shape[0]
-        key = (tuple(names), B, bool(fm), out_ld, tuple(str(batch[n].dtype) for n in names))
+        key = (tuple(names), B, bool(fm), out_ld, tuple(str(batch[n].dtype) for n in names), tuple(sorted(wide_names)))
         ent = model._shard_steps.get(key)
         if ent is None:
-            feats = [ShardedFeature(s.name, s.kind, '' if s.kind == NRX_DENSE else table_names[s.table], s.dim, s.bag_len, False, bool(s.fm_field))
+            feats = [ShardedFeature(s.name, s.kind, '' if s.kind == NRX_DENSE else table_names[s.table], s.dim, s.bag_len, s.wide_col >= 0,
+                                    bool(s.fm_field), s.kind != NRX_DENSE and table_names[s.table] in model._replicated_tables)
                      for s in plan.slots]
             bufs = [batch[n].detach().clone().contiguous() for n in names]
             wbufs = [None if m is None else batch[m].detach().clone().contiguous() for m in masks]
             arenas = {t: model.embedding_tables[t].weight.data for t in table_names}
             step = PreparedShardedStep(eng, feats, bufs, wbufs, arenas, out_ld=out_ld, train=True, slack=slack, one_sided=one_sided,
-                                       binary_masks=binary_masks, check_index=getattr(model, "index_check", "deferred") != "off")
+                                       binary_masks=binary_masks, check_index=getattr(model, "index_check", "deferred") != "off",
+                                       replicated_grads=any(f.replicated for f in feats))
             step._calls = 0
             step._direct_grad_default = direct_grad
             anchor = torch.zeros(1, device=bufs[0].device, requires_grad=True)
@@ -693,16 +858,17 @@ def shard_model_step_(model, rank: int, world: int, group=None, host_staged: boo
         step._calls += 1
         if step._calls % 64 == 1 and step._calls > 1:       # deferred: out-of-range ids / dropped lookups of the last 64 calls surface here, on every rank
             step.check()
+        want_wide = bool(wide_names)
         if torch.is_grad_enabled():
-            out, fmv = _ShardedStepFn.apply(step, model._sparse_sink, scale, need_out, bool(fm), anchor)
+            out, wide, fmv = _ShardedStepFn.apply(step, model._sparse_sink, scale, need_out, bool(fm), anchor, want_wide)
         else:
-            o, _, f_ = step.run()
-            out, fmv = (o if need_out else None), (f_ if fm else None)
+            o, w_, f_ = step.run()
+            out, wide, fmv = (o if need_out else None), (w_ if want_wide else None), (f_ if fm else None)
         if step._calls == 1:
             # a key's first call is checked at once (one all-reduce + one host read per new key): a batch whose blocks overflow raises here, on
             # every rank, before its backward and optimizer step.  Calls 2..64 are only checked on call 65 (or by check_shard_steps).
             step.check()
-        return out, None, fmv, list(dims), list(present)
+        return out, wide, fmv, list(dims), list(present)
 
     model._embed = _embed_step
     return model

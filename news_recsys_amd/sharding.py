@@ -232,6 +232,29 @@ class RowShardedEmbedding:
             dist.all_to_all_single(out, inp, out_split, in_split, group=self.group)
         return out
 
+    def _all_gather(self, out: torch.Tensor, inp: torch.Tensor) -> torch.Tensor:
+        """out [world * n] = every rank's inp [n], rank order (equal sizes)."""
+        if self.world == 1:
+            out.copy_(inp)
+        elif self.host_staged and out.is_cuda:
+            o = torch.empty(out.shape, dtype=out.dtype)
+            dist.all_gather(list(o.view(self.world, -1).unbind(0)), inp.cpu().reshape(-1), group=self.group)
+            out.copy_(o)
+        else:
+            dist.all_gather_into_tensor(out, inp, group=self.group)
+        return out
+
+    def _broadcast(self, t: torch.Tensor, src: int = 0) -> torch.Tensor:
+        """t = rank src's t on every rank."""
+        if self.world > 1:
+            if self.host_staged and t.is_cuda:
+                c = t.cpu()
+                dist.broadcast(c, src, group=self.group)
+                t.copy_(c)
+            else:
+                dist.broadcast(t, src, group=self.group)
+        return t
+
     def _all_reduce_max(self, t: torch.Tensor) -> torch.Tensor:
         if self.world > 1:
             if self.host_staged and t.is_cuda:

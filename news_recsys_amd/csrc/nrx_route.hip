@@ -626,7 +626,14 @@ __global__ __launch_bounds__(NRX_BLOCK) void pool_inbox_fwd_kernel(const PoolArg
     const int64_t nrows = a->rows[tix];
     const bool vec = (D & 3) == 0;
 
-    for (int k0 = q * 4; k0 < D; k0 += 4 * Q) {              // one pass when D <= 4Q (the launch picks Q for that)
+    // one pass when D <= 4Q (the launch picks Q for that).  EVERY lane of the group runs every pass: the entries are exchanged across the
+    // group inside it (__shfl), so a lane whose columns lie past D (D = 17, 24, 33, 300, ...) still loads and hands on its entries -- it only
+    // skips the row loads and the store.  (A lane that left the loop early fed the others stale {row, weight} words: wrong partial sums
+    // for every run longer than the active lanes' share of entries.)
+    const int passes = (D + 4 * Q - 1) / (4 * Q);
+    for (int pass = 0; pass < passes; ++pass) {
+        const int k0 = pass * 4 * Q + q * 4;
+        const bool live = k0 < D;
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int e0 = lo; e0 < hi; e0 += AHEAD) {
             int32_t row[AHEAD];
@@ -661,12 +668,13 @@ __global__ __launch_bounds__(NRX_BLOCK) void pool_inbox_fwd_kernel(const PoolArg
 #pragma unroll
             for (int u = 0; u < AHEAD; ++u) {
                 if ((uint32_t)row[u] >= (uint64_t)nrows) {
-                    if (q == 0 && k0 == 0 && w[u] != 0.f) nrx_report_oob(a->status, tix, base + e0 + u, row[u]);
+                    if (q == 0 && pass == 0 && w[u] != 0.f) nrx_report_oob(a->status, tix, base + e0 + u, row[u]);
                     row[u] = 0;
                     w[u] = 0.f;
                 }
                 const float* p = table + (int64_t)row[u] * D + k0;
-                if (vec) v[u] = nrx_ldg4(p, 0);
+                if (!live) v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                else if (vec) v[u] = nrx_ldg4(p, 0);
                 else { v[u] = make_float4(p[0], k0 + 1 < D ? p[1] : 0.f, k0 + 2 < D ? p[2] : 0.f, k0 + 3 < D ? p[3] : 0.f); }
             }
 #pragma unroll
@@ -675,6 +683,7 @@ __global__ __launch_bounds__(NRX_BLOCK) void pool_inbox_fwd_kernel(const PoolArg
                 acc.x += v[u].x * w[u]; acc.y += v[u].y * w[u]; acc.z += v[u].z * w[u]; acc.w += v[u].w * w[u];
             }
         }
+        if (!live) continue;
         float* dst = a->partial + ((int64_t)s * ntag + tag) * D + k0;
         dst[0] = acc.x;
         if (k0 + 1 < D) dst[1] = acc.y;

@@ -350,6 +350,16 @@ NRX_API int nrx_sparse_adam_step_bf16(uint16_t* const* tables, float* const* exp
                          const int64_t* n_unique_dev, float step_size, const float* step_size_dev, float beta1,
                          float beta2, float eps, float lr_times_weight_decay, uint64_t sr_seed, int64_t step,
                          const int64_t* step_dev, void* stream);
+/* nrx_sparse_adam_step_bf16 for tables that name a row by another index than the one the rounding stream knows it by (a row-sharded ARENA:
+ * key row a >= 1 of the arena of (rank, world) is global row (a - 1) * world + rank): the hash sees row * row_mul[t] + row_add[t] in the place of
+ * the key's row, t = the key's table (host arrays of n_tables entries; an arena's map is {world, rank - world}, a full table's {1, 0}).  Both
+ * NULL: the identity, nrx_sparse_adam_step_bf16's bits.  The arithmetic on the weight and the moments is unchanged, so a row-sharded run at any
+ * world size leaves the bf16 patterns of the unsharded run. */
+NRX_API int nrx_sparse_adam_step_bf16_rows(uint16_t* const* tables, float* const* exp_avg, float* const* exp_avg_sq, int32_t n_tables,
+                         int32_t dim, const int64_t* uniq_keys, const float* grads, int64_t n_unique,
+                         const int64_t* n_unique_dev, float step_size, const float* step_size_dev, float beta1,
+                         float beta2, float eps, float lr_times_weight_decay, uint64_t sr_seed, int64_t step,
+                         const int64_t* step_dev, const int64_t* row_mul, const int64_t* row_add, void* stream);
 
 /* Exact dense AdamW from row-sparse gradients ("exact-dense mode").  The reference trains every embedding table with one dense
  * torch.optim.AdamW over model.parameters() (src/model/sort/deep/model.py:54-65): every row moves every step.  nrx_rows_mark writes, for every
@@ -670,6 +680,11 @@ NRX_API int nrx_inbox_transpose(const int32_t* inbox_a, int32_t* out_a, const in
 NRX_API int nrx_gather_place_feat(const float* const* tables, const int64_t* table_rows, const int32_t* feat_col, int32_t n_feats, int32_t world,
                           int64_t capf, const int32_t* owner_ids, const int32_t* owner_pos, int32_t dim, float* const* peer_out,
                           int64_t out_ld, int64_t out_rows, int32_t* status, void* stream);
+/* nrx_gather_place_feat over bf16 arenas (uint16 bit patterns [rows, dim], 8-byte aligned; every arena of the launch): the rows are widened on
+ * load (exact) and stored fp32 -- the requester's concat equals nrx_gather_place_feat's on the widened arenas bit for bit. */
+NRX_API int nrx_gather_place_feat_bf16(const uint16_t* const* tables, const int64_t* table_rows, const int32_t* feat_col, int32_t n_feats, int32_t world,
+                          int64_t capf, const int32_t* owner_ids, const int32_t* owner_pos, int32_t dim, float* const* peer_out,
+                          int64_t out_ld, int64_t out_rows, int32_t* status, void* stream);
 /* The requester's half of the sharded backward (and any other permutation of upstream rows): values[dest[p], :dim] = the upstream row of lookup p
  * -- g_out[b, cols of feature f] with the FM term folded in as in nrx_embed_bwd (fm may be NULL) -- for the flat, feature-major lookups p = f *
  * batch + b of n_feats NRX_SPARSE features; dest[p] < 0: skipped.  Every written row is written once (dest is a partial permutation: the
@@ -758,6 +773,17 @@ NRX_API int nrx_route_bags_runs(const void* const* ids, const float* const* mask
 /* nrx_pool_inbox_fwd over run bounds that arrived with the exchange (block s of `run` = source s's send_run block for this owner): the pooling
  * launch alone; same partial sums bit for bit. */
 NRX_API int nrx_pool_inbox_fwd_runs(const float* const* tables, const int64_t* table_rows, int32_t n_tables, const int32_t* feat_table,
+                            int32_t n_feats, int64_t batch, int32_t world, int64_t cap, const int64_t* recv2d,
+                            const int32_t* inbox_rows, const float* inbox_w, const int32_t* run, int32_t dim, float* partial,
+                            int32_t* status, void* stream);
+/* nrx_pool_inbox_fwd / nrx_pool_inbox_fwd_runs over bf16 tables (uint16 bit patterns [rows, dim]; 8-byte aligned where dim % 4 == 0; every table
+ * of the launch): rows widened on load (exact), fp32 partial sums formed in the same order -- the fp32 call's result on the widened tables bit
+ * for bit. */
+NRX_API int nrx_pool_inbox_fwd_bf16(const uint16_t* const* tables, const int64_t* table_rows, int32_t n_tables, const int32_t* feat_table,
+                            int32_t n_feats, int64_t batch, int32_t world, int64_t cap, const int64_t* recv2d,
+                            const int32_t* inbox_rows, const int32_t* inbox_tag, const float* inbox_w, int32_t dim,
+                            float* partial, void* workspace, int32_t* status, void* stream);
+NRX_API int nrx_pool_inbox_fwd_runs_bf16(const uint16_t* const* tables, const int64_t* table_rows, int32_t n_tables, const int32_t* feat_table,
                             int32_t n_feats, int64_t batch, int32_t world, int64_t cap, const int64_t* recv2d,
                             const int32_t* inbox_rows, const float* inbox_w, const int32_t* run, int32_t dim, float* partial,
                             int32_t* status, void* stream);

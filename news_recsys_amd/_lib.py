@@ -131,6 +131,7 @@ SIGNATURES = {
     "nrx_pool_inbox_owner_ids": (C.c_int, [_i64, _i32, _i64, _i32, _i64, _p, _p, _p, _i32, _p, _p, _p]),
     "nrx_pool_order_remap": (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p]),
     "nrx_gather_place_feat": (C.c_int, [C.POINTER(_p), C.POINTER(_i64), C.POINTER(_i32), _i32, _i32, _i64, _p, _p, _i32, C.POINTER(_p), _i64, _i64, _p, _p]),
+    "nrx_gather_place_feat_bf16": (C.c_int, [C.POINTER(_p), C.POINTER(_i64), C.POINTER(_i32), _i32, _i32, _i64, _p, _p, _i32, C.POINTER(_p), _i64, _i64, _p, _p]),
     "nrx_embed_bwd_scatter": (C.c_int, [C.POINTER(NrxFeature), _i32, _i64, _i32, _p, _i64, _p, _i64, C.POINTER(NrxFmGrad), _p, _p, _p]),
     "nrx_bucketize_workspace": (_i64, [_i64, _i32]),
     "nrx_bucketize_by_owner": (C.c_int, [_p, _i32, _i64, _i32, _p, _p, _p, _p, _p]),
@@ -156,11 +157,15 @@ SIGNATURES = {
                                       C.POINTER(_p), _p, _p, _p, _p]),
     "nrx_pool_inbox_fwd_runs": (C.c_int, [C.POINTER(_p), C.POINTER(_i64), _i32, C.POINTER(_i32), _i32, _i64, _i32, _i64, _p, _p, _p, _p, _i32,
                                           _p, _p, _p]),
+    "nrx_pool_inbox_fwd_runs_bf16": (C.c_int, [C.POINTER(_p), C.POINTER(_i64), _i32, C.POINTER(_i32), _i32, _i64, _i32, _i64, _p, _p, _p, _p, _i32,
+                                               _p, _p, _p]),
     "nrx_pool_inbox_runs_words": (C.c_int, [_i64, _i32, _i64, _i32, _i64, _p, _p, _p, _i32, _p, _p, _p, _p]),
     "nrx_route_bags": (C.c_int, [C.POINTER(_p), C.POINTER(_p), C.POINTER(_i32), _i32, _i32, _i64, _i32, _i64, _p, _p, _p, _p, _p, _p, _p]),
     "nrx_pool_inbox_workspace": (_i64, [_i32, _i64, _i32]),
     "nrx_pool_inbox_fwd": (C.c_int, [C.POINTER(_p), C.POINTER(_i64), _i32, C.POINTER(_i32), _i32, _i64, _i32, _i64, _p, _p, _p, _p, _i32,
                                      _p, _p, _p, _p]),
+    "nrx_pool_inbox_fwd_bf16": (C.c_int, [C.POINTER(_p), C.POINTER(_i64), _i32, C.POINTER(_i32), _i32, _i64, _i32, _i64, _p, _p, _p, _p, _i32,
+                                          _p, _p, _p, _p]),
     "nrx_pool_inbox_bwd": (C.c_int, [C.POINTER(_p), C.POINTER(_i64), _i32, C.POINTER(_i32), _i32, _i64, _i32, _i64, _p, _p, _p, _p, _i32,
                                      _p, _i32, _p]),
     "nrx_gather_inbox": (C.c_int, [C.POINTER(_p), C.POINTER(_i64), _i32, C.POINTER(_i32), _i32, _i32, _i64, _p, _p, _i32, _p, _p, _p]),
@@ -183,6 +188,8 @@ SIGNATURES = {
                                        C.c_float, _p]),
     "nrx_sparse_adam_step_bf16": (C.c_int, [_p, _p, _p, _i32, _i32, _p, _p, _i64, _p, C.c_float, _p, C.c_float, C.c_float, C.c_float,
                                             C.c_float, C.c_uint64, _i64, _p, _p]),
+    "nrx_sparse_adam_step_bf16_rows": (C.c_int, [_p, _p, _p, _i32, _i32, _p, _p, _i64, _p, C.c_float, _p, C.c_float, C.c_float, C.c_float,
+                                                 C.c_float, C.c_uint64, _i64, _p, C.POINTER(_i64), C.POINTER(_i64), _p]),
     "nrx_rows_to_dense": (C.c_int, [_p, _i32, _i32, _p, _p, _i64, _p, _i32, _p]),
     "nrx_topk_workspace": (_i64, [_i64, _i64, _i32]),
     "nrx_topk_ip": (C.c_int, [_p, _i64, _i32, _p, _i64, _i32, _p, _p, _p, _p, _p, _p]),

@@ -524,7 +524,7 @@ __global__ __launch_bounds__(NRX_BLOCK) void inbox_gather_ring_kernel(const Inbo
 //     sum_o sum_{k in o} (w_k / den) * row_k   ==   array_feature_pooling's  (sum_k w_k row_k) / den      (base_model.py:278-282)
 // up to fp32 summation order (stated tolerance rtol 1e-6).
 struct PoolArgs {
-    float* table[NRX_MAX_FEATURES];        // weight tables (fwd) or grad tables (bwd)
+    float* table[NRX_MAX_FEATURES];        // weight tables (fwd; uint16 = bf16 rows in the TS = uint16_t launches, whatever the type says) or grad tables (bwd)
     int64_t rows[NRX_MAX_FEATURES];
     int32_t feat_table[NRX_MAX_FEATURES];
     int32_t n_feats;
@@ -603,7 +603,11 @@ __global__ __launch_bounds__(NRX_BLOCK) void pool_runs_words_kernel(const PoolAr
     }
 }
 
-template <int QLOG2>
+// TS = the tables' storage (one per launch): float, or uint16_t for bf16 tables (nrx_pool_inbox_fwd_bf16 / _runs_bf16).  Fixed at compile time, so
+// the AHEAD row loads of a pass still issue before one wait; the rows are widened in registers (exact), the partial sums stay fp32 and are
+// formed in the same order: a bf16 call equals the fp32 call on the widened table bit for bit.
+typedef unsigned nrx_pool_u32x2 __attribute__((ext_vector_type(2)));
+template <int QLOG2, typename TS = float>
 __global__ __launch_bounds__(NRX_BLOCK) void pool_inbox_fwd_kernel(const PoolArgs args_in_kernarg, const int32_t* __restrict__ run) {
     const NRX_CONST PoolArgs* a = nrx_kernarg<PoolArgs>();
     constexpr int Q = 1 << QLOG2;
@@ -665,6 +669,10 @@ __global__ __launch_bounds__(NRX_BLOCK) void pool_inbox_fwd_kernel(const PoolArg
                 }
             }
             float4 v[AHEAD];
+            // bf16: this loop keeps the RAW words (4 columns in 2 dwords; v[] is not used) and the summing loop widens them -- widened here, the
+            // value would be used behind the branch around its load and the compiler waits vmcnt(0) behind every one of the AHEAD loads (seen
+            // in the ISA); and 2 registers per row in flight instead of 4 keep the occupancy of the fp32 form
+            [[maybe_unused]] nrx_pool_u32x2 raw[AHEAD];
 #pragma unroll
             for (int u = 0; u < AHEAD; ++u) {
                 if ((uint32_t)row[u] >= (uint64_t)nrows) {
@@ -672,14 +680,25 @@ __global__ __launch_bounds__(NRX_BLOCK) void pool_inbox_fwd_kernel(const PoolArg
                     row[u] = 0;
                     w[u] = 0.f;
                 }
-                const float* p = table + (int64_t)row[u] * D + k0;
-                if (!live) v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-                else if (vec) v[u] = nrx_ldg4(p, 0);
-                else { v[u] = make_float4(p[0], k0 + 1 < D ? p[1] : 0.f, k0 + 2 < D ? p[2] : 0.f, k0 + 3 < D ? p[3] : 0.f); }
+                if constexpr (sizeof(TS) == 2) {
+                    const uint16_t* p = reinterpret_cast<const uint16_t*>(table) + (int64_t)row[u] * D + k0;
+                    raw[u] = nrx_pool_u32x2{0u, 0u};
+                    if (live && vec) raw[u] = *(const NRX_GLOBAL nrx_pool_u32x2*)(p);
+                    else if (live) {
+                        raw[u].x = (uint32_t)p[0] | (k0 + 1 < D ? (uint32_t)p[1] << 16 : 0u);
+                        raw[u].y = (k0 + 2 < D ? (uint32_t)p[2] : 0u) | (k0 + 3 < D ? (uint32_t)p[3] << 16 : 0u);
+                    }
+                } else {
+                    const float* p = table + (int64_t)row[u] * D + k0;
+                    if (!live) v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    else if (vec) v[u] = nrx_ldg4(p, 0);
+                    else { v[u] = make_float4(p[0], k0 + 1 < D ? p[1] : 0.f, k0 + 2 < D ? p[2] : 0.f, k0 + 3 < D ? p[3] : 0.f); }
+                }
             }
 #pragma unroll
             for (int u = 0; u < AHEAD; ++u) {
 #pragma clang fp contract(off)
+                if constexpr (sizeof(TS) == 2) v[u] = nrx_bf16x4_to_f32(raw[u].x, raw[u].y);      // (zero words -- a lane or a column past D -- widen to zeros)
                 acc.x += v[u].x * w[u]; acc.y += v[u].y * w[u]; acc.z += v[u].z * w[u]; acc.w += v[u].w * w[u];
             }
         }
@@ -1125,14 +1144,15 @@ extern "C" int nrx_route_bags(const void* const* ids, const float* const* weight
 namespace {
 int fill_pool_args(PoolArgs& a, float* const* tables, const int64_t* table_rows, int32_t n_tables, const int32_t* feat_table,
                    int32_t n_feats, int64_t batch, int32_t world, int64_t cap, const int64_t* recv2d, const int32_t* inbox_rows,
-                   const int32_t* inbox_tag, const float* inbox_w, int32_t dim, const char* who) {
+                   const int32_t* inbox_tag, const float* inbox_w, int32_t dim, const char* who, bool bf16 = false) {
     NRX_REQUIRE(tables && table_rows && n_tables >= 1 && n_tables <= NRX_MAX_FEATURES, "%s: n_tables must be in [1, %d]", who, NRX_MAX_FEATURES);
     NRX_REQUIRE(feat_table && n_feats >= 1 && n_feats <= NRX_MAX_FEATURES, "%s: n_feats must be in [1, %d]", who, NRX_MAX_FEATURES);
     NRX_REQUIRE(world >= 1 && world <= 64 && cap >= 1 && dim >= 1 && dim <= 1024 && batch >= 1, "%s: bad world/cap/dim/batch", who);
     NRX_REQUIRE(recv2d && inbox_rows && inbox_tag && inbox_w, "%s: null buffer", who);
     for (int i = 0; i < n_tables; ++i) {
         NRX_REQUIRE(tables[i] != nullptr, "%s: table %d is null", who, i);
-        NRX_REQUIRE((dim & 3) != 0 || nrx_aligned16(tables[i]), "%s: table %d must be 16-byte aligned", who, i);
+        NRX_REQUIRE((dim & 3) != 0 || (reinterpret_cast<uintptr_t>(tables[i]) & (bf16 ? 7u : 15u)) == 0, "%s: table %d must be %d-byte aligned", who, i,
+                    bf16 ? 8 : 16);
         a.table[i] = tables[i];
         a.rows[i] = table_rows[i];
     }
@@ -1163,16 +1183,17 @@ extern "C" int64_t nrx_pool_inbox_workspace(int32_t n_feats, int64_t batch, int3
     return (int64_t)world * n_feats * batch * 2 * (int64_t)sizeof(int32_t);      // bytes: run start / end per (source, tag)
 }
 
-extern "C" int nrx_pool_inbox_fwd(const float* const* tables, const int64_t* table_rows, int32_t n_tables, const int32_t* feat_table,
+namespace {
+template <typename TS>
+int pool_inbox_fwd_launch(const char* who, const void* const* tables, const int64_t* table_rows, int32_t n_tables, const int32_t* feat_table,
                                   int32_t n_feats, int64_t batch, int32_t world, int64_t cap, const int64_t* recv2d,
                                   const int32_t* inbox_rows, const int32_t* inbox_tag, const float* inbox_w, int32_t dim,
                                   float* partial, void* workspace, int32_t* status, void* stream) {
-    NRX_TRACE();
     PoolArgs a;
-    int rc = fill_pool_args(a, const_cast<float* const*>(tables), table_rows, n_tables, feat_table, n_feats, batch, world, cap, recv2d,
-                            inbox_rows, inbox_tag, inbox_w, dim, "nrx_pool_inbox_fwd");
+    int rc = fill_pool_args(a, reinterpret_cast<float* const*>(const_cast<void* const*>(tables)), table_rows, n_tables, feat_table, n_feats, batch, world, cap, recv2d,
+                            inbox_rows, inbox_tag, inbox_w, dim, who, sizeof(TS) == 2);
     if (rc != NRX_OK) return rc;
-    NRX_REQUIRE(partial != nullptr && workspace != nullptr, "nrx_pool_inbox_fwd: null partial / workspace");
+    NRX_REQUIRE(partial != nullptr && workspace != nullptr, "%s: null partial / workspace", who);
     a.partial = partial;
     a.status = status;
     a.skip_row0 = 0;
@@ -1185,28 +1206,28 @@ extern "C" int nrx_pool_inbox_fwd(const float* const* tables, const int64_t* tab
     const int tb = NRX_BLOCK >> ql;
     const dim3 grid((unsigned)((ntag + tb - 1) / tb), (unsigned)world);
     switch (ql) {
-#define NRX_CASE(QL_) case QL_: hipLaunchKernelGGL((pool_inbox_fwd_kernel<QL_>), grid, dim3(NRX_BLOCK), 0, st, a, (const int32_t*)run); break;
+#define NRX_CASE(QL_) case QL_: hipLaunchKernelGGL((pool_inbox_fwd_kernel<QL_, TS>), grid, dim3(NRX_BLOCK), 0, st, a, (const int32_t*)run); break;
         NRX_CASE(0) NRX_CASE(1) NRX_CASE(2) NRX_CASE(3) NRX_CASE(4) NRX_CASE(5)
-        default: hipLaunchKernelGGL((pool_inbox_fwd_kernel<6>), grid, dim3(NRX_BLOCK), 0, st, a, (const int32_t*)run); break;
+        default: hipLaunchKernelGGL((pool_inbox_fwd_kernel<6, TS>), grid, dim3(NRX_BLOCK), 0, st, a, (const int32_t*)run); break;
 #undef NRX_CASE
     }
-    NRX_LAUNCH_CHECK("nrx_pool_inbox_fwd");
+    NRX_LAUNCH_CHECK(who);
     return NRX_OK;
 }
 
 // The owner's pooling launch alone, over run bounds that ARRIVED (nrx_route_bags_runs wrote them at the source; block s of `run` = what source s
 // sent): no memset, no marking pass over the entries.
-extern "C" int nrx_pool_inbox_fwd_runs(const float* const* tables, const int64_t* table_rows, int32_t n_tables, const int32_t* feat_table,
+template <typename TS>
+int pool_inbox_fwd_runs_launch(const char* who, const void* const* tables, const int64_t* table_rows, int32_t n_tables, const int32_t* feat_table,
                                        int32_t n_feats, int64_t batch, int32_t world, int64_t cap, const int64_t* recv2d,
                                        const int32_t* inbox_rows, const float* inbox_w, const int32_t* run, int32_t dim, float* partial,
                                        int32_t* status, void* stream) {
-    NRX_TRACE();
     PoolArgs a;
-    NRX_REQUIRE(run != nullptr, "nrx_pool_inbox_fwd_runs: null run");
-    int rc = fill_pool_args(a, const_cast<float* const*>(tables), table_rows, n_tables, feat_table, n_feats, batch, world, cap, recv2d,
-                            inbox_rows, run /* (no tag array: never read) */, inbox_w, dim, "nrx_pool_inbox_fwd_runs");
+    NRX_REQUIRE(run != nullptr, "%s: null run", who);
+    int rc = fill_pool_args(a, reinterpret_cast<float* const*>(const_cast<void* const*>(tables)), table_rows, n_tables, feat_table, n_feats, batch, world, cap, recv2d,
+                            inbox_rows, run /* (no tag array: never read) */, inbox_w, dim, who, sizeof(TS) == 2);
     if (rc != NRX_OK) return rc;
-    NRX_REQUIRE(partial != nullptr, "nrx_pool_inbox_fwd_runs: null partial");
+    NRX_REQUIRE(partial != nullptr, "%s: null partial", who);
     a.inbox_tag = nullptr;
     a.partial = partial;
     a.status = status;
@@ -1217,13 +1238,51 @@ extern "C" int nrx_pool_inbox_fwd_runs(const float* const* tables, const int64_t
     const int tb = NRX_BLOCK >> ql;
     const dim3 grid((unsigned)((ntag + tb - 1) / tb), (unsigned)world);
     switch (ql) {
-#define NRX_CASE(QL_) case QL_: hipLaunchKernelGGL((pool_inbox_fwd_kernel<QL_>), grid, dim3(NRX_BLOCK), 0, st, a, run); break;
+#define NRX_CASE(QL_) case QL_: hipLaunchKernelGGL((pool_inbox_fwd_kernel<QL_, TS>), grid, dim3(NRX_BLOCK), 0, st, a, run); break;
         NRX_CASE(0) NRX_CASE(1) NRX_CASE(2) NRX_CASE(3) NRX_CASE(4) NRX_CASE(5)
-        default: hipLaunchKernelGGL((pool_inbox_fwd_kernel<6>), grid, dim3(NRX_BLOCK), 0, st, a, run); break;
+        default: hipLaunchKernelGGL((pool_inbox_fwd_kernel<6, TS>), grid, dim3(NRX_BLOCK), 0, st, a, run); break;
 #undef NRX_CASE
     }
-    NRX_LAUNCH_CHECK("nrx_pool_inbox_fwd_runs");
+    NRX_LAUNCH_CHECK(who);
     return NRX_OK;
+}
+}  // namespace
+
+extern "C" int nrx_pool_inbox_fwd(const float* const* tables, const int64_t* table_rows, int32_t n_tables, const int32_t* feat_table,
+                                  int32_t n_feats, int64_t batch, int32_t world, int64_t cap, const int64_t* recv2d,
+                                  const int32_t* inbox_rows, const int32_t* inbox_tag, const float* inbox_w, int32_t dim,
+                                  float* partial, void* workspace, int32_t* status, void* stream) {
+    NRX_TRACE();
+    return pool_inbox_fwd_launch<float>("nrx_pool_inbox_fwd", reinterpret_cast<const void* const*>(tables), table_rows, n_tables, feat_table, n_feats, batch, world,
+                                        cap, recv2d, inbox_rows, inbox_tag, inbox_w, dim, partial, workspace, status, stream);
+}
+
+extern "C" int nrx_pool_inbox_fwd_runs(const float* const* tables, const int64_t* table_rows, int32_t n_tables, const int32_t* feat_table,
+                                       int32_t n_feats, int64_t batch, int32_t world, int64_t cap, const int64_t* recv2d,
+                                       const int32_t* inbox_rows, const float* inbox_w, const int32_t* run, int32_t dim, float* partial,
+                                       int32_t* status, void* stream) {
+    NRX_TRACE();
+    return pool_inbox_fwd_runs_launch<float>("nrx_pool_inbox_fwd_runs", reinterpret_cast<const void* const*>(tables), table_rows, n_tables, feat_table, n_feats,
+                                             batch, world, cap, recv2d, inbox_rows, inbox_w, run, dim, partial, status, stream);
+}
+
+// The two launches over bf16 tables (uint16 bit patterns [rows, dim]; 8-byte aligned where dim % 4 == 0): see pool_inbox_fwd_kernel.
+extern "C" int nrx_pool_inbox_fwd_bf16(const uint16_t* const* tables, const int64_t* table_rows, int32_t n_tables, const int32_t* feat_table,
+                                       int32_t n_feats, int64_t batch, int32_t world, int64_t cap, const int64_t* recv2d,
+                                       const int32_t* inbox_rows, const int32_t* inbox_tag, const float* inbox_w, int32_t dim,
+                                       float* partial, void* workspace, int32_t* status, void* stream) {
+    NRX_TRACE();
+    return pool_inbox_fwd_launch<uint16_t>("nrx_pool_inbox_fwd_bf16", reinterpret_cast<const void* const*>(tables), table_rows, n_tables, feat_table, n_feats, batch,
+                                           world, cap, recv2d, inbox_rows, inbox_tag, inbox_w, dim, partial, workspace, status, stream);
+}
+
+extern "C" int nrx_pool_inbox_fwd_runs_bf16(const uint16_t* const* tables, const int64_t* table_rows, int32_t n_tables, const int32_t* feat_table,
+                                            int32_t n_feats, int64_t batch, int32_t world, int64_t cap, const int64_t* recv2d,
+                                            const int32_t* inbox_rows, const float* inbox_w, const int32_t* run, int32_t dim, float* partial,
+                                            int32_t* status, void* stream) {
+    NRX_TRACE();
+    return pool_inbox_fwd_runs_launch<uint16_t>("nrx_pool_inbox_fwd_runs_bf16", reinterpret_cast<const void* const*>(tables), table_rows, n_tables, feat_table,
+                                                n_feats, batch, world, cap, recv2d, inbox_rows, inbox_w, run, dim, partial, status, stream);
 }
 
 extern "C" int nrx_pool_inbox_runs_words(int64_t table_rows, int32_t n_feats, int64_t batch, int32_t world, int64_t cap, const int64_t* recv2d,

@@ -537,12 +537,14 @@ __global__ __launch_bounds__(NRX_BLOCK) void inbox_transpose_kernel(const int32_
 // (peer[s] + pos * ld + col[f]) instead of into a [world * capf, n * dim] row buffer that an all-to-all carries back and a final launch re-reads.
 // A lane group of Q lanes owns a pseudo-sample b' = s * capf + k and walks the features with GP_R row loads in flight; owner id 0 with a
 // position >= 0 is a lookup of the padding id: zeros are written (position < 0: an empty slot, skipped).
+// TS = the arenas' storage (one per launch): float, or uint16_t for bf16 arenas (nrx_gather_place_feat_bf16) -- a lane then loads its 4 columns
+// as 8 bytes and widens them in registers (exact); what it stores into the requester's concat is fp32 either way.
 #ifndef NRX_GP_R
 #define NRX_GP_R 8
 #endif
 constexpr int GP_R = NRX_GP_R;
 struct GatherPlaceArgs {
-    const float* table[NRX_MAX_FEATURES];      // arena base (row 0 = the dummy row)
+    const float* table[NRX_MAX_FEATURES];      // arena base (row 0 = the dummy row); uint16 (bf16) rows in the TS = uint16_t launches, whatever the type says
     int64_t rows[NRX_MAX_FEATURES];            // arena rows
     int32_t col[NRX_MAX_FEATURES];
     float* peer[RF_MAX_WORLD];
@@ -554,7 +556,8 @@ struct GatherPlaceArgs {
 };
 static_assert(sizeof(GatherPlaceArgs) <= 3584, "kernarg budget");
 
-template <int QLOG2>
+typedef unsigned nrx_gp_u32x2 __attribute__((ext_vector_type(2)));
+template <int QLOG2, typename TS = float>
 __global__ __launch_bounds__(NRX_BLOCK) void gather_place_feat_kernel(const GatherPlaceArgs args_in_kernarg) {
     const NRX_CONST GatherPlaceArgs* a = nrx_kernarg<GatherPlaceArgs>();
     constexpr int Q = 1 << QLOG2, TB = NRX_BLOCK / Q;
@@ -576,16 +579,34 @@ __global__ __launch_bounds__(NRX_BLOCK) void gather_place_feat_kernel(const Gath
         };
         auto process = [&](int f0, const int32_t* id, int32_t* pos) {
             float4 v[GP_R];
+            // bf16: the loop below issues the eight row loads UNCONDITIONALLY and keeps the raw words; the second loop widens them where they are
+            // stored.  A slot that reads nothing (empty, padding id, out of range) loads the arena's row 0 and its value is replaced by zeros
+            // where it is used.  A load behind `if (id != 0)` is a branch around a load: the compiler then waits vmcnt(0) at every one of
+            // them and the eight go out one behind the other (seen in the ISA; bag_rows_bf16 in nrx_embed.hip is built the same way)
+            [[maybe_unused]] nrx_gp_u32x2 raw[GP_R];
+            [[maybe_unused]] bool use[GP_R];
 #pragma unroll
             for (int r = 0; r < GP_R; ++r) {
                 const int f = f0 + r < n ? f0 + r : n - 1;
                 v[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (sizeof(TS) == 2) {
+                    // (the base and the row count are wave-uniform: read as scalars BEFORE the per-lane tests, or the compiler fetches them
+                    // with vector loads behind those tests and waits for them in front of every row load)
+                    const uint64_t tb = reinterpret_cast<uint64_t>(a->table[f]);
+                    const uint32_t tb_lo = __builtin_amdgcn_readfirstlane((uint32_t)tb), tb_hi = __builtin_amdgcn_readfirstlane((uint32_t)(tb >> 32));
+                    const uint32_t nr = __builtin_amdgcn_readfirstlane((uint32_t)(a->rows[f] > 0x7fffffff ? 0x7fffffff : a->rows[f]));
+                    const NRX_GLOBAL nrx_gp_u32x2* base = (const NRX_GLOBAL nrx_gp_u32x2*)(((uint64_t)tb_hi << 32) | tb_lo);
+                    use[r] = f0 + r < n && pos[r] >= 0 && id[r] > 0 && (uint32_t)id[r] < nr;
+                    raw[r] = __builtin_nontemporal_load(base + ((int64_t)(use[r] ? id[r] : 0) * Q + q));
+                }
                 if (f0 + r >= n || pos[r] < 0) { pos[r] = -1; continue; }
                 if (id[r] < 0 || (int64_t)id[r] >= a->rows[f]) {          // cannot be a row of this shard: zeros, reported
                     if (q == 0) nrx_report_oob(a->status, f, b, id[r]);
                     continue;
                 }
-                if (id[r] != 0) v[r] = nrx_ldg4_nt(a->table[f], (int64_t)id[r] * Q + q);
+                if constexpr (sizeof(TS) != 2) {
+                    if (id[r] != 0) v[r] = nrx_ldg4_nt(a->table[f], (int64_t)id[r] * Q + q);
+                }
             }
 #pragma unroll
             for (int r = 0; r < GP_R; ++r) {
@@ -594,6 +615,9 @@ __global__ __launch_bounds__(NRX_BLOCK) void gather_place_feat_kernel(const Gath
                 if ((int64_t)pos[r] >= a->out_rows) {                    // a position outside the requester's batch (it came from a peer): dropped, reported
                     if (q == 0) nrx_report_oob(a->status, f, b, pos[r]);
                     continue;
+                }
+                if constexpr (sizeof(TS) == 2) {
+                    if (use[r]) v[r] = nrx_bf16x4_to_f32(raw[r].x, raw[r].y);
                 }
                 nrx_stg4(out, ((int64_t)pos[r] * a->ld + a->col[f]) / 4 + q, v[r]);
             }
@@ -674,26 +698,31 @@ extern "C" int nrx_shard_dest_combine(const int32_t* slot, const int32_t* dest_r
     return NRX_OK;
 }
 
-extern "C" int nrx_gather_place_feat(const float* const* tables, const int64_t* table_rows, const int32_t* feat_col, int32_t n_feats, int32_t world,
+namespace {
+template <typename TS>
+int gather_place_feat_launch(const char* who, const void* const* tables, const int64_t* table_rows, const int32_t* feat_col, int32_t n_feats, int32_t world,
                                      int64_t capf, const int32_t* owner_ids, const int32_t* owner_pos, int32_t dim, float* const* peer_out,
                                      int64_t out_ld, int64_t out_rows, int32_t* status, void* stream) {
-    NRX_TRACE();
-    NRX_REQUIRE(tables && table_rows && feat_col && owner_ids && owner_pos && peer_out, "nrx_gather_place_feat: null argument");
-    NRX_REQUIRE(n_feats >= 1 && n_feats <= NRX_MAX_FEATURES && world >= 1 && world <= RF_MAX_WORLD && capf >= 1, "nrx_gather_place_feat: bad sizes");
+    NRX_REQUIRE(tables && table_rows && feat_col && owner_ids && owner_pos && peer_out, "%s: null argument", who);
+    NRX_REQUIRE(n_feats >= 1 && n_feats <= NRX_MAX_FEATURES && world >= 1 && world <= RF_MAX_WORLD && capf >= 1, "%s: bad sizes", who);
     if (!(dim == 16 || dim == 32 || dim == 64 || dim == 128 || dim == 256) || (out_ld & 3) != 0) {
-        nrx_set_error("nrx_gather_place_feat: dim must be 16 / 32 / 64 / 128 / 256 and out_ld a multiple of 4");
+        nrx_set_error("%s: dim must be 16 / 32 / 64 / 128 / 256 and out_ld a multiple of 4", who);
         return NRX_ERR_UNSUPPORTED;
     }
     GatherPlaceArgs a;
     memset(&a, 0, sizeof(a));
     for (int i = 0; i < n_feats; ++i) {
-        NRX_REQUIRE(tables[i] != nullptr && nrx_aligned16(tables[i]) && (feat_col[i] & 3) == 0, "nrx_gather_place_feat: feature %d: aligned table and column", i);
-        a.table[i] = tables[i];
+        // (whole rows of 4 Q columns: 16 Q bytes in fp32, 8 Q in bf16 -- an aligned base keeps every lane's 16 / 8-byte load aligned)
+        NRX_REQUIRE(tables[i] != nullptr && (reinterpret_cast<uintptr_t>(tables[i]) & (sizeof(TS) == 2 ? 7u : 15u)) == 0 && (feat_col[i] & 3) == 0,
+                    "%s: feature %d: aligned table and column", who, i);
+        // (the bf16 form reads row 0 -- an arena's dummy row -- for the slots that read nothing: it must exist)
+        NRX_REQUIRE(sizeof(TS) != 2 || table_rows[i] >= 1, "%s: feature %d: a bf16 arena has at least its dummy row", who, i);
+        a.table[i] = reinterpret_cast<const float*>(tables[i]);
         a.rows[i] = table_rows[i];
         a.col[i] = feat_col[i];
     }
     for (int s = 0; s < world; ++s) {
-        NRX_REQUIRE(peer_out[s] != nullptr && nrx_aligned16(peer_out[s]), "nrx_gather_place_feat: peer %d: null / unaligned buffer", s);
+        NRX_REQUIRE(peer_out[s] != nullptr && nrx_aligned16(peer_out[s]), "%s: peer %d: null / unaligned buffer", who, s);
         a.peer[s] = peer_out[s];
     }
     a.oid = owner_ids;
@@ -710,13 +739,30 @@ extern "C" int nrx_gather_place_feat(const float* const* tables, const int64_t* 
     int64_t blocks = (a.bp + tb - 1) / tb;
     if (blocks > 8192) blocks = 8192;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (ql == 2) hipLaunchKernelGGL((gather_place_feat_kernel<2>), dim3((unsigned)blocks), dim3(NRX_BLOCK), 0, st, a);
-    else if (ql == 3) hipLaunchKernelGGL((gather_place_feat_kernel<3>), dim3((unsigned)blocks), dim3(NRX_BLOCK), 0, st, a);
-    else if (ql == 4) hipLaunchKernelGGL((gather_place_feat_kernel<4>), dim3((unsigned)blocks), dim3(NRX_BLOCK), 0, st, a);
-    else if (ql == 5) hipLaunchKernelGGL((gather_place_feat_kernel<5>), dim3((unsigned)blocks), dim3(NRX_BLOCK), 0, st, a);
-    else hipLaunchKernelGGL((gather_place_feat_kernel<6>), dim3((unsigned)blocks), dim3(NRX_BLOCK), 0, st, a);
-    NRX_LAUNCH_CHECK("nrx_gather_place_feat");
+    if (ql == 2) hipLaunchKernelGGL((gather_place_feat_kernel<2, TS>), dim3((unsigned)blocks), dim3(NRX_BLOCK), 0, st, a);
+    else if (ql == 3) hipLaunchKernelGGL((gather_place_feat_kernel<3, TS>), dim3((unsigned)blocks), dim3(NRX_BLOCK), 0, st, a);
+    else if (ql == 4) hipLaunchKernelGGL((gather_place_feat_kernel<4, TS>), dim3((unsigned)blocks), dim3(NRX_BLOCK), 0, st, a);
+    else if (ql == 5) hipLaunchKernelGGL((gather_place_feat_kernel<5, TS>), dim3((unsigned)blocks), dim3(NRX_BLOCK), 0, st, a);
+    else hipLaunchKernelGGL((gather_place_feat_kernel<6, TS>), dim3((unsigned)blocks), dim3(NRX_BLOCK), 0, st, a);
+    NRX_LAUNCH_CHECK(who);
     return NRX_OK;
+}
+}  // namespace
+
+extern "C" int nrx_gather_place_feat(const float* const* tables, const int64_t* table_rows, const int32_t* feat_col, int32_t n_feats, int32_t world,
+                                     int64_t capf, const int32_t* owner_ids, const int32_t* owner_pos, int32_t dim, float* const* peer_out,
+                                     int64_t out_ld, int64_t out_rows, int32_t* status, void* stream) {
+    NRX_TRACE();
+    return gather_place_feat_launch<float>("nrx_gather_place_feat", reinterpret_cast<const void* const*>(tables), table_rows, feat_col, n_feats, world, capf,
+                                           owner_ids, owner_pos, dim, peer_out, out_ld, out_rows, status, stream);
+}
+
+extern "C" int nrx_gather_place_feat_bf16(const uint16_t* const* tables, const int64_t* table_rows, const int32_t* feat_col, int32_t n_feats, int32_t world,
+                                          int64_t capf, const int32_t* owner_ids, const int32_t* owner_pos, int32_t dim, float* const* peer_out,
+                                          int64_t out_ld, int64_t out_rows, int32_t* status, void* stream) {
+    NRX_TRACE();
+    return gather_place_feat_launch<uint16_t>("nrx_gather_place_feat_bf16", reinterpret_cast<const void* const*>(tables), table_rows, feat_col, n_feats, world,
+                                              capf, owner_ids, owner_pos, dim, peer_out, out_ld, out_rows, status, stream);
 }
 
 extern "C" int64_t nrx_route_feat_state_bytes(int32_t n_feats, int64_t batch, int32_t world) {

@@ -2102,6 +2102,15 @@ struct SparseAdamBf16Args {
     const int64_t* step_dev;    // optional: step read on the device (captured loops)
 };
 static_assert(sizeof(SparseAdamBf16Args) <= 3584, "kernarg budget");
+// MAP launches (nrx_sparse_adam_step_bf16_rows) carry the row maps BEHIND the unmapped launch's arguments, in a struct of their own (the
+// unmapped launches keep their kernarg segment): the row the hash sees is key row * row_mul[t] + row_add[t] -- a row-sharded arena names a
+// row by its local index, the rounding stream by the global one
+struct SparseAdamBf16MapArgs {
+    SparseAdamBf16Args b;
+    int64_t row_mul[NRX_MAX_FEATURES];
+    int64_t row_add[NRX_MAX_FEATURES];
+};
+static_assert(sizeof(SparseAdamBf16MapArgs) <= 3584, "kernarg budget");
 
 __device__ __forceinline__ uint64_t sr_mix(uint64_t z) {
     z += 0x9E3779B97F4A7C15ull;
@@ -2117,9 +2126,9 @@ __device__ __forceinline__ uint16_t sr_bf16(float w, uint64_t h_row, int64_t col
     return (uint16_t)((u + r) >> 16);
 }
 
-template <int QLOG2, bool VEC>
-__global__ __launch_bounds__(NRX_BLOCK) void sparse_adam_bf16_kernel(const SparseAdamBf16Args args_in_kernarg) {
-    const NRX_CONST SparseAdamBf16Args* ab = nrx_kernarg<SparseAdamBf16Args>();
+template <int QLOG2, bool VEC, bool MAP = false, typename ARGS = SparseAdamBf16Args>
+__global__ __launch_bounds__(NRX_BLOCK) void sparse_adam_bf16_kernel(const ARGS args_in_kernarg) {
+    const NRX_CONST SparseAdamBf16Args* ab = nrx_kernarg<SparseAdamBf16Args>();       // (MAP: the leading member of SparseAdamBf16MapArgs)
     const NRX_CONST SparseAdamArgs* a = &ab->base;
     constexpr int Q = 1 << QLOG2;
     constexpr int TB = NRX_BLOCK / Q;
@@ -2152,7 +2161,12 @@ __global__ __launch_bounds__(NRX_BLOCK) void sparse_adam_bf16_kernel(const Spars
         p[r] = reinterpret_cast<uint16_t*>(a->table[tc]) + rc * D;
         pm[r] = a->m[tc] + rc * a->mom_ld[tc];
         pv[r] = a->v[tc] + rc * a->mom_ld[tc];
-        h[r] = sr_mix(sr_mix(h_step ^ (uint64_t)tc) ^ (uint64_t)rc);
+        int64_t hashed = rc;
+        if constexpr (MAP) {
+            const NRX_CONST SparseAdamBf16MapArgs* am = nrx_kernarg<SparseAdamBf16MapArgs>();
+            hashed = rc * am->row_mul[tc] + am->row_add[tc];
+        }
+        h[r] = sr_mix(sr_mix(h_step ^ (uint64_t)tc) ^ (uint64_t)hashed);
     }
     if (VEC) {
         for (int k = q * 4; k < D; k += 4 * Q) {
@@ -2596,19 +2610,20 @@ extern "C" int nrx_sparse_adam_step(float* const* tables, float* const* exp_avg,
     return NRX_OK;
 }
 
-extern "C" int nrx_sparse_adam_step_bf16(uint16_t* const* tables, float* const* exp_avg, float* const* exp_avg_sq, int32_t n_tables,
+namespace {
+int sparse_adam_bf16_launch(const char* who, const int64_t* row_mul, const int64_t* row_add, uint16_t* const* tables, float* const* exp_avg, float* const* exp_avg_sq, int32_t n_tables,
                                          int32_t dim, const int64_t* uniq_keys, const float* grads, int64_t n_unique,
                                          const int64_t* n_unique_dev, float step_size, const float* step_size_dev, float beta1,
                                          float beta2, float eps, float lr_times_weight_decay, uint64_t sr_seed, int64_t step,
                                          const int64_t* step_dev, void* stream) {
-    NRX_TRACE();
-    NRX_REQUIRE(n_tables >= 1 && n_tables <= NRX_MAX_FEATURES && dim >= 1 && n_unique >= 0, "nrx_sparse_adam_step_bf16: bad argument");
+    NRX_REQUIRE(n_tables >= 1 && n_tables <= NRX_MAX_FEATURES && dim >= 1 && n_unique >= 0, "%s: bad argument", who);
     if (n_unique == 0) return NRX_OK;
-    NRX_REQUIRE(tables && exp_avg && exp_avg_sq && uniq_keys && grads, "nrx_sparse_adam_step_bf16: null buffer");
-    SparseAdamBf16Args ab;
+    NRX_REQUIRE(tables && exp_avg && exp_avg_sq && uniq_keys && grads, "%s: null buffer", who);
+    SparseAdamBf16MapArgs am;
+    SparseAdamBf16Args& ab = am.b;
     SparseAdamArgs& a = ab.base;
     for (int t = 0; t < n_tables; ++t) {       // moment layouts as nrx_sparse_adam_step
-        NRX_REQUIRE(tables[t] && exp_avg[t] && exp_avg_sq[t], "nrx_sparse_adam_step_bf16: table %d: null pointer", t);
+        NRX_REQUIRE(tables[t] && exp_avg[t] && exp_avg_sq[t], "%s: table %d: null pointer", who, t);
         a.table[t] = reinterpret_cast<float*>(tables[t]);
         a.m[t] = exp_avg[t];
         a.v[t] = exp_avg_sq[t];
@@ -2629,6 +2644,15 @@ extern "C" int nrx_sparse_adam_step_bf16(uint16_t* const* tables, float* const* 
     ab.seed = sr_seed;
     ab.step = step;
     ab.step_dev = step_dev;
+    const bool map = row_mul != nullptr && row_add != nullptr;
+    if (map) {
+        memset(am.row_mul, 0, sizeof(am.row_mul));
+        memset(am.row_add, 0, sizeof(am.row_add));
+        for (int t = 0; t < n_tables; ++t) {
+            am.row_mul[t] = row_mul[t];
+            am.row_add[t] = row_add[t];
+        }
+    }
     int ql = 0;
     while ((4 << ql) < dim && ql < 6) ++ql;
     bool vec = (dim & 3) == 0 && nrx_aligned16(grads);
@@ -2638,13 +2662,37 @@ extern "C" int nrx_sparse_adam_step_bf16(uint16_t* const* tables, float* const* 
     const int64_t groups = (n_unique + 3) / 4;
     const unsigned grid = (unsigned)((groups + tb - 1) / tb);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define NRX_SA(QL_) if (vec) hipLaunchKernelGGL((sparse_adam_bf16_kernel<QL_, true>), dim3(grid), dim3(NRX_BLOCK), 0, st, ab); \
+#define NRX_SA(QL_) if (vec && map) hipLaunchKernelGGL((sparse_adam_bf16_kernel<QL_, true, true, SparseAdamBf16MapArgs>), dim3(grid), dim3(NRX_BLOCK), 0, st, am); \
+                    else if (map) hipLaunchKernelGGL((sparse_adam_bf16_kernel<QL_, false, true, SparseAdamBf16MapArgs>), dim3(grid), dim3(NRX_BLOCK), 0, st, am); \
+                    else if (vec) hipLaunchKernelGGL((sparse_adam_bf16_kernel<QL_, true>), dim3(grid), dim3(NRX_BLOCK), 0, st, ab); \
                     else hipLaunchKernelGGL((sparse_adam_bf16_kernel<QL_, false>), dim3(grid), dim3(NRX_BLOCK), 0, st, ab)
     switch (ql) {
         case 0: NRX_SA(0); break; case 1: NRX_SA(1); break; case 2: NRX_SA(2); break; case 3: NRX_SA(3); break;
         case 4: NRX_SA(4); break; case 5: NRX_SA(5); break; default: NRX_SA(6); break;
     }
 #undef NRX_SA
-    NRX_LAUNCH_CHECK("nrx_sparse_adam_step_bf16");
+    NRX_LAUNCH_CHECK(who);
     return NRX_OK;
+}
+}  // namespace
+
+extern "C" int nrx_sparse_adam_step_bf16(uint16_t* const* tables, float* const* exp_avg, float* const* exp_avg_sq, int32_t n_tables,
+                                         int32_t dim, const int64_t* uniq_keys, const float* grads, int64_t n_unique,
+                                         const int64_t* n_unique_dev, float step_size, const float* step_size_dev, float beta1,
+                                         float beta2, float eps, float lr_times_weight_decay, uint64_t sr_seed, int64_t step,
+                                         const int64_t* step_dev, void* stream) {
+    NRX_TRACE();
+    return sparse_adam_bf16_launch("nrx_sparse_adam_step_bf16", nullptr, nullptr, tables, exp_avg, exp_avg_sq, n_tables, dim, uniq_keys, grads, n_unique,
+                                   n_unique_dev, step_size, step_size_dev, beta1, beta2, eps, lr_times_weight_decay, sr_seed, step, step_dev, stream);
+}
+
+extern "C" int nrx_sparse_adam_step_bf16_rows(uint16_t* const* tables, float* const* exp_avg, float* const* exp_avg_sq, int32_t n_tables,
+                                              int32_t dim, const int64_t* uniq_keys, const float* grads, int64_t n_unique,
+                                              const int64_t* n_unique_dev, float step_size, const float* step_size_dev, float beta1,
+                                              float beta2, float eps, float lr_times_weight_decay, uint64_t sr_seed, int64_t step,
+                                              const int64_t* step_dev, const int64_t* row_mul, const int64_t* row_add, void* stream) {
+    NRX_TRACE();
+    NRX_REQUIRE((row_mul == nullptr) == (row_add == nullptr), "nrx_sparse_adam_step_bf16_rows: row_mul and row_add come together (both null: identity)");
+    return sparse_adam_bf16_launch("nrx_sparse_adam_step_bf16_rows", row_mul, row_add, tables, exp_avg, exp_avg_sq, n_tables, dim, uniq_keys, grads, n_unique,
+                                   n_unique_dev, step_size, step_size_dev, beta1, beta2, eps, lr_times_weight_decay, sr_seed, step, step_dev, stream);
 }

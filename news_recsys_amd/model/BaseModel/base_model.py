@@ -419,8 +419,14 @@ class BaseModel(LightningModule):
                 if self._sparse_sink is None:
                     self._sparse_sink = ops.SparseGradSink()
                 sink = self._sparse_sink
+            row_maps = None
+            if getattr(self, "_shard_bf16", False):
+                # bf16 arenas of the bound sharded step (shard_model_step_(bf16_tables=True)): the rounding hash takes the GLOBAL row
+                from ...shard_step import arena_row_map
+                eng = self._shard_engine
+                row_maps = [arena_row_map(eng.rank, eng.world) if getattr(e, "arena", False) else (1, 0) for e in self.embedding_tables.values()]
             optimizer = SparseDenseAdam(table_params, [p for p in self.parameters() if id(p) not in ids], lr=hp.lr, fused_sink=sink,
-                                        exact=self.sparse_grad == "exact", sr_seed=self.sr_seed)
+                                        exact=self.sparse_grad == "exact", sr_seed=self.sr_seed, row_maps=row_maps)
         else:
             from ..model_utils.optim import dense_adamw
             optimizer = dense_adamw(self.parameters(), lr=hp.lr, betas=(0.9, 0.999))     # torch.optim.AdamW; its one-pass kernel on the GPU

@@ -41,14 +41,18 @@ class FusedSparseAdam:
     bf16 tables (torch.bfloat16; all tables of the optimizer then) keep fp32 moments and step through
     `nrx_sparse_adam_step_bf16`: the fp32 update of the widened row, rounded back to bf16 stochastically with bits that
     depend on (sr_seed, step, table, row, column) only -- sr_seed and the step count are in state_dict(), so a resumed run
-    continues the same rounding stream.  `table` is the table's position in `params`, which bf16 tables therefore require."""
+    continues the same rounding stream.  `table` is the table's position in `params`, which bf16 tables therefore require.
+    `row` is the key's row, or -- row_maps -- an affine function of it: a row-sharded bf16 arena (shard_step.make_arena) names a row by
+    its local index, the hash takes the global one (shard_step.arena_row_map), so a sharded run leaves the unsharded run's bit patterns."""
 
     def __init__(self, sink: "ops.SparseGradSink", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False,
-                 params=None, sr_seed=0):
+                 params=None, sr_seed=0, row_maps=None):
         """capturable=True keeps the step counter and the bias-corrected step size on the device (like
         torch.optim.Adam(capturable=True)) so step() can be captured in a HIP graph (graph.GraphedStep); lr is
         then fixed at capture time.  params (optional): the table tensors in a stable order -- state_dict() then
-        keys the moments by position in that list, so a checkpoint restores into a freshly built model."""
+        keys the moments by position in that list, so a checkpoint restores into a freshly built model.
+        row_maps (optional, bf16 tables): one (row_mul, row_add) per entry of `params` -- the stochastic rounding hashes
+        row * row_mul + row_add; None, or (1, 0) for a table: the key's row itself."""
         self.sink, self.lr, self.betas, self.eps, self.weight_decay = sink, lr, betas, eps, weight_decay
         self.capturable = bool(capturable)
         self.params = list(params) if params is not None else None
@@ -62,11 +66,24 @@ class FusedSparseAdam:
         self._maps = []          # per-table slot maps of the two-list merge (made on first use)
         self.pair_merge = True   # two backward groups of one width: merge by marking (False: the sort-based _merge)
         self.sr_seed = int(sr_seed) & ((1 << 64) - 1)     # stochastic rounding of bf16 tables
+        self.row_maps = None
+        if row_maps is not None:
+            self.set_row_maps(row_maps)
         if self.params is not None and any(t.dtype is torch.bfloat16 for t in self.params):
             # the rounding hash names a table by its position here: pinned to the params order, so a run resumed from a checkpoint
             # (whose load registers the tables in that order) hashes every table as the uninterrupted run does
             for t in self.params:
                 self._register(t)
+
+    def set_row_maps(self, row_maps):
+        """(row_mul, row_add) per entry of `params` (see __init__); None: the identity for every table."""
+        if row_maps is None:
+            self.row_maps = None
+            return
+        row_maps = [(int(m), int(a)) for m, a in row_maps]
+        if self.params is None or len(row_maps) != len(self.params):
+            raise ValueError("FusedSparseAdam: row_maps needs params=<the table list> and one (row_mul, row_add) per table of it")
+        self.row_maps = row_maps
 
     def _register(self, t: torch.Tensor) -> int:
         i = self._index.get(id(t))
@@ -150,7 +167,18 @@ class FusedSparseAdam:
             raise NotImplementedError("FusedSparseAdam: bf16 and fp32 tables in one optimizer")
         # the rounding stream's step index: the host count, or (capturable) the device count a captured loop advances
         step_dev = self._t_dev.to(torch.int64).reshape(1) if (n_bf16 and self._t_dev is not None) else None
+        rmul = radd = None
+        if n_bf16 and self.row_maps is not None and any(m != (1, 0) for m in self.row_maps):
+            maps = [self.row_maps[self._stable_index(t)] for t in self.tables]      # (bf16 tables are all in params: _register)
+            rmul, radd = (C.c_int64 * n)(*[m for m, _ in maps]), (C.c_int64 * n)(*[a for _, a in maps])
         def adam(keys, vals):
+            if rmul is not None:
+                ops.check(lib.nrx_sparse_adam_step_bf16_rows(tp, mp, vp, n, dim, keys.data_ptr(), vals.data_ptr(), keys.numel(), None,
+                                                             step_size, ss_dev.data_ptr() if ss_dev is not None else None, b1, b2, self.eps,
+                                                             self.lr * self.weight_decay, self.sr_seed, self.t,
+                                                             step_dev.data_ptr() if step_dev is not None else None, rmul, radd,
+                                                             torch.cuda.current_stream(keys.device).cuda_stream), "nrx_sparse_adam_step_bf16_rows")
+                return
             if n_bf16:
                 ops.check(lib.nrx_sparse_adam_step_bf16(tp, mp, vp, n, dim, keys.data_ptr(), vals.data_ptr(), keys.numel(), None,
                                                         step_size, ss_dev.data_ptr() if ss_dev is not None else None, b1, b2, self.eps,
@@ -335,10 +363,10 @@ class ExactDenseAdamW(FusedSparseAdam):
 
 class SparseDenseAdam(torch.optim.Optimizer):
     def __init__(self, sparse_params, dense_params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, fused_sink=None,
-                 capturable=False, exact=False, sr_seed=0):
+                 capturable=False, exact=False, sr_seed=0, row_maps=None):
         """fused_sink: an ops.SparseGradSink -> the tables are updated by FusedSparseAdam from the sink instead of
         torch.optim.SparseAdam from COO .grad tensors.  exact (with fused_sink): by ExactDenseAdamW -- the reference's dense AdamW over every
-        row, weight decay included, fed from the sink."""
+        row, weight decay included, fed from the sink.  row_maps: FusedSparseAdam's (bf16 arenas of the bound sharded step)."""
         sparse_params, dense_params = list(sparse_params), list(dense_params)
         groups = [{"params": sparse_params, "sparse": True}]
         if dense_params:
@@ -346,11 +374,14 @@ class SparseDenseAdam(torch.optim.Optimizer):
         super().__init__(groups, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         if exact and fused_sink is None:
             raise ValueError("SparseDenseAdam(exact=True) needs fused_sink")
+        if row_maps is not None and (exact or fused_sink is None):
+            raise ValueError("SparseDenseAdam: row_maps belong to FusedSparseAdam (fused_sink, not exact)")
         if fused_sink is None and any(p.dtype is torch.bfloat16 for p in sparse_params):
             raise TypeError("SparseDenseAdam: bf16 tables train only with the fused sink (torch.optim.SparseAdam needs COO gradients, "
                             "which bf16 tables do not form); use embeddings.sparse_grad: fused")
         self._sparse = (ExactDenseAdamW(fused_sink, sparse_params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable) if exact else
-                        FusedSparseAdam(fused_sink, lr=lr, betas=betas, eps=eps, capturable=capturable, params=sparse_params, sr_seed=sr_seed)
+                        FusedSparseAdam(fused_sink, lr=lr, betas=betas, eps=eps, capturable=capturable, params=sparse_params, sr_seed=sr_seed,
+                                        row_maps=row_maps)
                         if fused_sink is not None
                         else torch.optim.SparseAdam(sparse_params, lr=lr, betas=betas, eps=eps))
         self._dense = (torch.optim.AdamW(dense_params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable)

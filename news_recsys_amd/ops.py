@@ -2537,9 +2537,11 @@ def unique_inverse(ids: torch.Tensor):
 
 
 def refuse_bf16_tables(tables, what: str) -> None:
-    """The sharded engine reads and writes fp32 rows only: bf16 tables (embeddings.table_dtype: bf16) are refused, never misread."""
+    """The unbound sharded engine (the segmented / inbox wrappers, sharding.shard_model_) reads and writes fp32 rows only: bf16 tables
+    (embeddings.table_dtype: bf16) are refused, never misread.  The bound step takes them (shard_step.PreparedShardedStep)."""
     if any(t is not None and t.dtype is torch.bfloat16 for t in tables):
-        raise NotImplementedError(f"{what}: bf16 embedding tables are not supported by the sharded engine")
+        raise NotImplementedError(f"{what}: bf16 embedding tables are not supported by the unbound sharded engine (its wrappers read fp32 rows); "
+                                  "the bound step takes them: shard_step.PreparedShardedStep / shard_model_step_(..., bf16_tables=True)")
 
 
 def _inbox_common(tables, feat_table):

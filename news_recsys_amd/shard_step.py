@@ -26,7 +26,12 @@ Bag features (C4's history) keep sharding.py's pooled channel for the forward --
 owner) comes back -- and get a bound backward here: the requester sends every owner the samples' upstream rows, `nrx_pool_inbox_expand` turns the
 owner's inbox entries into pseudo-lookups (owner id, w * upstream row) of ONE single-valued feature over the arena, and the same planned
 reduction takes over (row-sparse, deterministic; nrx_pool_inbox_bwd's float atomics into a dense shard gradient are gone).  A table fed by a
-pooled group AND a single-valued group (DSSM's news table) leaves two (keys, values) lists, which FusedSparseAdam merges into one update per row."""
+pooled group AND a single-valued group (DSSM's news table) leaves two (keys, values) lists, which FusedSparseAdam merges into one update per row.
+
+bf16 arenas (make_arena(dtype=torch.bfloat16), shard_model_step_(bf16_tables=True)): the launches that read a table -- the placing
+gather, the owner's pooling, the owner's buffered forward and the final launch's replicated tables -- take their bf16 forms (rows widened on
+load); the backward reads no table.  FusedSparseAdam hashes the GLOBAL row of an arena row into the stochastic rounding (arena_row_map), so
+the ranks' arenas hold the unsharded bf16 model's bit patterns at any world size."""
 from __future__ import annotations
 
 import ctypes as C
@@ -41,23 +46,43 @@ from .sharding import RowShardedEmbedding, ShardedFeature, local_row_count
 
 # --------------------------------------------------------------------------------- arenas
 def make_arena(rows: int, dim: int, rank: int, world: int, device, full: Optional[torch.Tensor] = None,
-               generator: Optional[torch.Generator] = None) -> torch.Tensor:
+               generator: Optional[torch.Generator] = None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """This rank's shard of a [rows, dim] table WITH the leading dummy row: [1 + local_row_count, dim]; arena[1 + k] = global row
     k * world + rank.  `full` (optional): the unsharded table to take the rows from (scatter-on-load); else N(0, 1) rows (nn.Embedding's init,
     base_model.py:164).  arena[0] is zero and stays zero; on rank 0, arena[1] is the global padding row: zero, never looked up (owner id 0
-    stands for it), never trained."""
-    if full is not None:
-        ops.refuse_bf16_tables([full], "make_arena")
+    stands for it), never trained.
+    dtype: torch.float32, or torch.bfloat16 (embeddings.table_dtype: bf16) -- from a bf16 `full` a copy (exact), else the N(0, 1) draw (the
+    fp32 arena's own draw) rounded to nearest.  That draw is ONE call on an fp32 temporary of the shard's size (freed on return: a transient
+    of twice the bf16 arena): drawn in chunks, the generator's stream -- and with it the equality with the fp32 arena -- would depend on
+    the chunking.  shard_model_step_ never draws (it copies the model's tables)."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"make_arena: dtype must be torch.float32 or torch.bfloat16, got {dtype}")
+    if full is not None and full.dtype is not dtype:
+        if full.dtype is torch.bfloat16:
+            raise NotImplementedError("make_arena: a bf16 table makes a bf16 arena: pass dtype=torch.bfloat16 "
+                                      "(shard_model_step_(..., bf16_tables=True) does)")
+        raise TypeError(f"make_arena: `full` is {full.dtype}, the arena {dtype}: convert the table first (its rounding is the caller's choice)")
     n = local_row_count(rows, rank, world)
-    a = torch.empty((n + 1, dim), dtype=torch.float32, device=device)
+    a = torch.empty((n + 1, dim), dtype=dtype, device=device)
     if full is not None:
         a[1:].copy_(full[rank::world])
+    elif dtype is torch.bfloat16:
+        a[1:].copy_(torch.empty((n, dim), dtype=torch.float32, device=device).normal_(generator=generator))
     else:
         a[1:].normal_(generator=generator)
     a[0].zero_()
     if rank == 0 and n > 0:
         a[1].zero_()
     return a
+
+
+def arena_row_map(rank: int, world: int) -> tuple:
+    """(row_mul, row_add) with arena row a >= 1 of make_arena(..., rank, world) = global row a * row_mul + row_add (= (a - 1) * world + rank): what
+    the stochastic rounding of a bf16 arena hashes in the place of the arena row (optim.FusedSparseAdam(row_maps=...),
+    nrx_sparse_adam_step_bf16_rows), so that a row draws the bits it draws in the unsharded table.  A full or replicated table's map is (1, 0)."""
+    if not 0 <= rank < world:
+        raise ValueError("arena_row_map: need 0 <= rank < world")
+    return world, rank - world
 
 
 def replicated_layout(tables: Sequence[tuple], world: int) -> dict:
@@ -82,7 +107,9 @@ def arena_shard(arena: torch.Tensor) -> torch.Tensor:
 
 class PreparedShardedStep:
     """A bound, re-launchable sharded forward + backward over the SAME id tensors (refill them in place): see the module docstring.
-    `arenas` maps table name -> arena tensor (make_arena).  Replicated tables (ShardedFeature.replicated) are plain full tables."""
+    `arenas` maps table name -> arena tensor (make_arena).  Replicated tables (ShardedFeature.replicated) are plain full tables.
+    bf16 arenas and replicated tables (make_arena(dtype=torch.bfloat16); all tables of the step then): every launch that reads a table takes its
+    bf16 form (rows widened on load, exact) -- outputs, gradient rows and everything on the wire stay fp32; the backward reads no table."""
 
     def __init__(self, eng: RowShardedEmbedding, feats: Sequence[ShardedFeature], inputs, weights, arenas: Dict[str, torch.Tensor],
                  out_ld: Optional[int] = None, out: Optional[torch.Tensor] = None, fm: Optional[torch.Tensor] = None, train: bool = True,
@@ -119,6 +146,13 @@ class PreparedShardedStep:
         self.status = torch.zeros(4, dtype=torch.int32, device=inputs[0].device) if check_index else None
         W = eng.world
         self.keep = [inputs, weights, arenas]
+        used = {f.table for f in feats if f.kind != NRX_DENSE}
+        dts = {arenas[t].dtype for t in used}
+        if len(dts) > 1 or not dts <= {torch.float32, torch.bfloat16}:
+            raise NotImplementedError("PreparedShardedStep: the arenas and replicated tables of one step must share ONE dtype, fp32 or bf16 "
+                                      f"(got {sorted(str(d) for d in dts)}): the owner's launches and FusedSparseAdam take one storage per launch")
+        self.bf16 = dts == {torch.bfloat16}
+        tflag = _lib.NRX_FEAT_TABLE_BF16 if self.bf16 else 0
         groups, pooled = eng.plan_groups(feats)
         for gi, idxs in enumerate(groups):
             if gi not in pooled and any(feats[i].kind != NRX_SPARSE for i in idxs):
@@ -129,6 +163,10 @@ class PreparedShardedStep:
         final_weights = list(weights)
         slack = eng.slack if slack is None else slack
         plan = eng._final_plan(feats, groups, pooled)
+        if self.bf16:       # the final launch reads the replicated tables themselves (the routed features' rows come back fp32)
+            import dataclasses
+            plan = ops.EmbedPlan([dataclasses.replace(sl, flags=sl.flags | tflag) if (f.kind != NRX_DENSE and f.replicated) else sl
+                                  for sl, f in zip(plan.slots, feats)], out_width=plan.out_width, wide_width=plan.wide_width, use_fm=plan.use_fm)
         B0 = inputs[0].shape[0]
         dev0 = inputs[0].device
         self.dev0 = dev0
@@ -221,7 +259,7 @@ class PreparedShardedStep:
                     g["inbox_pos"] = torch.full((W, n, capf), -1, dtype=torch.int32, device=dev)
                     g["opos"] = torch.full((n, Bp), -1, dtype=torch.int32, device=dev)
             # the owner's side: a plain batch of Bp pseudo-samples, n single-valued features, concat [Bp, n * D]
-            oslots = [ops.Slot(feats[i].name, NRX_SPARSE, table_names.index(feats[i].table), D, 0, k * D) for k, i in enumerate(idxs)]
+            oslots = [ops.Slot(feats[i].name, NRX_SPARSE, table_names.index(feats[i].table), D, 0, k * D, flags=tflag) for k, i in enumerate(idxs)]
             g["owner_fwd"] = ops.PreparedEmbed(ops.EmbedPlan(oslots, out_width=n * D), tabs, [g["oid"][k] for k in range(n)], [None] * n,
                                                need_out=not placed,      # (placed: never run -- the descriptor of the owner's pseudo-batch for the backward)
                                                check_index=check_index and not placed)
@@ -355,8 +393,9 @@ class PreparedShardedStep:
             if self.bwd is not None and self.plan_mode == "forward" and not g["pooled"] and not self.bwd[self.groups.index(g)]["direct"]:
                 self.bwd[self.groups.index(g)]["owner"].plan_ahead()
             if placed:
-                rc = lib.nrx_gather_place_feat(g["tp"], g["tr"], g["cols"], g["n"], W, g["capf"], g["oid"].data_ptr(), g["opos"].data_ptr(), g["D"],
-                                               self._peer_ptrs, self.ld, self.out.shape[0], ops._ptr(self.status), stream)
+                gather = lib.nrx_gather_place_feat_bf16 if self.bf16 else lib.nrx_gather_place_feat
+                rc = gather(g["tp"], g["tr"], g["cols"], g["n"], W, g["capf"], g["oid"].data_ptr(), g["opos"].data_ptr(), g["D"],
+                            self._peer_ptrs, self.ld, self.out.shape[0], ops._ptr(self.status), stream)
                 if rc:
                     ops.check(rc, "nrx_gather_place_feat")
                 return
@@ -470,7 +509,8 @@ class PreparedShardedStep:
                 g_recv = g_send if W == 1 else torch.empty_like(g_send)
                 oid = torch.zeros(W * cap, dtype=torch.int32, device=g["dev"])
                 # the owner's pseudo-batch: ONE single-valued feature of W * cap pseudo-lookups over the arena (never run forward: a descriptor)
-                pfwd = ops.PreparedEmbed(ops.EmbedPlan([ops.Slot(g["table_names"][0], NRX_SPARSE, 0, D, 0, 0)], out_width=D), [arena], [oid], [None],
+                pfwd = ops.PreparedEmbed(ops.EmbedPlan([ops.Slot(g["table_names"][0], NRX_SPARSE, 0, D, 0, 0,
+                                                                 flags=_lib.NRX_FEAT_TABLE_BF16 if self.bf16 else 0)], out_width=D), [arena], [oid], [None],
                                          need_out=False)
                 b = dict(pooled=True, direct=False, g_send=g_send, g_recv=g_recv, oid=oid, cols=[plan.slots[i].out_col for i in g["idxs"]], binary=self.binary_masks)
                 if self.binary_masks:
@@ -779,7 +819,7 @@ def replicated_table_names(model, replicate: Sequence[str] = (), replicate_below
 
 def shard_model_step_(model, rank: int, world: int, group=None, host_staged: bool = False, slack: float = 0.05, binary_masks: bool = True,
                       one_sided: Optional[bool] = None, direct_grad: Optional[bool] = None, grad_average: bool = True,
-                      replicate: Sequence[str] = (), replicate_below_bytes: int = 0):
+                      replicate: Sequence[str] = (), replicate_below_bytes: int = 0, bf16_tables: bool = False):
     """Convert a BaseModel in place to row-sharded tables TRAINED BY THE BOUND STEP (the counterpart of sharding.shard_model_, whose backward
     forms dense shard gradients): every `embedding_tables[name].weight` becomes this rank's ARENA ([1 + local rows, D]: row 0 the dummy row,
     rows 1.. = global rows rank::world), `_embed` runs a PreparedShardedStep bound per (feature set, batch size) -- the batch's ids are copied into
@@ -796,8 +836,18 @@ def shard_model_step_(model, rank: int, world: int, group=None, host_staged: boo
     replicate / replicate_below_bytes (replicated_table_names): tables kept in FULL on every rank ([rows, D], requires_grad False, made equal to
     rank 0's at conversion, listed in model._replicated_tables): their features read them locally (no exchange) and the bound step reduces
     their row-sparse gradient over the ranks in rank order (PreparedShardedStep(replicated_grads=True)); FusedSparseAdam updates them from
-    the sink like the arenas.  Wide features (Wide&Deep) must be replicated.  Defaults: every table row-sharded."""
-    ops.refuse_bf16_tables([e.weight for e in model.embedding_tables.values()], "shard_model_step_")
+    the sink like the arenas.  Wide features (Wide&Deep) must be replicated.  Defaults: every table row-sharded.
+    bf16_tables: convert a model built with embeddings.table_dtype: bf16 -- bf16 arenas and replicated tables, fp32 moments; FusedSparseAdam
+    rounds stochastically with the GLOBAL row in its hash (configure_optimizers() wires arena_row_map), so after every optimizer step the
+    arenas hold the bf16 bit patterns of the unsharded bf16 model trained on the rank-major concatenation of the batches.  A bf16 model
+    without it is refused (the conversion is opt-in), an fp32 model with it is a ValueError."""
+    is_bf16 = [e.weight.dtype is torch.bfloat16 for e in model.embedding_tables.values()]
+    if any(is_bf16) and not bf16_tables:
+        raise NotImplementedError("shard_model_step_: the model's embedding tables are bf16 (embeddings.table_dtype: bf16): pass bf16_tables=True "
+                                  "to shard them as bf16 arenas")
+    if bf16_tables and not all(is_bf16):
+        raise ValueError("shard_model_step_(bf16_tables=True) needs a model built with embeddings.table_dtype: bf16 (its tables are "
+                         f"{sorted({str(e.weight.dtype) for e in model.embedding_tables.values()})})")
     import torch.nn as nn
     from .sharding import RowShardedEmbedding, ShardedFeature
     eng = RowShardedEmbedding(rank, world, group, None, slack=slack, host_staged=host_staged, overflow_policy="defer")
@@ -814,7 +864,7 @@ def shard_model_step_(model, rank: int, world: int, group=None, host_staged: boo
             new.weight = nn.Parameter(full, requires_grad=False)   # (updated in place by FusedSparseAdam from the sink, never through .grad)
             model.embedding_tables[name] = new
             continue
-        arena = make_arena(emb.num_embeddings, w.shape[1], rank, world, w.device, full=w)
+        arena = make_arena(emb.num_embeddings, w.shape[1], rank, world, w.device, full=w, dtype=w.dtype)
         new = nn.Embedding(arena.shape[0], arena.shape[1])
         new.weight = nn.Parameter(arena, requires_grad=False)      # (updated in place by FusedSparseAdam from the sink, never through .grad)
         new.global_rows = emb.num_embeddings
@@ -822,6 +872,7 @@ def shard_model_step_(model, rank: int, world: int, group=None, host_staged: boo
         model.embedding_tables[name] = new
     model._shard_engine = eng
     model._shard_steps = {}
+    model._shard_bf16 = bool(bf16_tables)      # (configure_optimizers() then wires the arenas' row maps into FusedSparseAdam)
     scale = 1.0 / world if (grad_average and world > 1) else 1.0
 
     def _embed_step(batch, feature_names, fm=False, wide_names=(), out_ld=None, need_out=True):
@@ -841,7 +892,8 @@ def shard_model_step_(model, rank: int, world: int, group=None, host_staged: boo
                      for s in plan.slots]
             bufs = [batch[n].detach().clone().contiguous() for n in names]
             wbufs = [None if m is None else batch[m].detach().clone().contiguous() for m in masks]
-            arenas = {t: model.embedding_tables[t].weight.data for t in table_names}
+            # (bf16: the Parameters themselves -- FusedSparseAdam names a bf16 table in the rounding hash by its position in `params`, found by identity)
+            arenas = {t: (model.embedding_tables[t].weight if bf16_tables else model.embedding_tables[t].weight.data) for t in table_names}
             step = PreparedShardedStep(eng, feats, bufs, wbufs, arenas, out_ld=out_ld, train=True, slack=slack, one_sided=one_sided,
                                        binary_masks=binary_masks, check_index=getattr(model, "index_check", "deferred") != "off",
                                        replicated_grads=any(f.replicated for f in feats))

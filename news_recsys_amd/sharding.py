@@ -246,6 +246,9 @@ class RowShardedEmbedding:
 
     def _broadcast(self, t: torch.Tensor, src: int = 0) -> torch.Tensor:
         """t = rank src's t on every rank."""
+        if self.world > 1 and t.dtype is torch.bfloat16:        # (gloo moves neither bf16 nor int16: the bit patterns travel as bytes)
+            self._broadcast(t.view(torch.uint8), src)
+            return t
         if self.world > 1:
             if self.host_staged and t.is_cuda:
                 c = t.cpu()
@@ -831,9 +834,12 @@ class PreparedShardedForward:
             if feats[i].table not in table_names:
                 table_names.append(feats[i].table)
         loc = [tables[t] for t in table_names]
+        bf16 = any(t.dtype is torch.bfloat16 for t in loc)      # (the pooling launch takes one storage: nrx_pool_inbox_fwd*_bf16)
+        if bf16 and not all(t.dtype is torch.bfloat16 for t in loc):
+            raise NotImplementedError("the tables of one pooled exchange group must share one dtype (fp32 or bf16)")
         # a table with fewer rows than ranks leaves some ranks an EMPTY shard (a 5-row category table at world 8): its tensor has no address, and
         # the pooling launch -- which reads row 0 for the entries it masks out -- wants one: a zero row stands in (the row count stays 0, so
-        # every entry that reaches this owner is reported as out of range and contributes nothing)
+        # every entry that reaches this owner is reported as out of range and contributes nothing; zero bits are zeros in bf16 too)
         stand_in = torch.zeros((1, D), dtype=torch.float32, device=dev)
         masks = [weights[i] if feats[i].kind != NRX_BAG_MEAN else None for i in idxs]
         wn = [torch.empty((B, feats[i].bag_len), dtype=torch.float32, device=dev) for i in idxs]
@@ -852,7 +858,7 @@ class PreparedShardedForward:
                  pws=torch.empty(max(1, self.lib.nrx_pool_inbox_workspace(n, B, W)), dtype=torch.uint8, device=dev),
                  ret=torch.empty((W, n * B, D), dtype=torch.float32, device=dev),
                  tp=(C.c_void_p * len(loc))(*[(t if t.shape[0] else stand_in).data_ptr() for t in loc]), tr=(C.c_int64 * len(loc))(*[t.shape[0] for t in loc]),
-                 nt=len(loc), ft=(C.c_int32 * n)(*[table_names.index(feats[i].table) for i in idxs]), dev=dev, stand_in=stand_in)
+                 nt=len(loc), ft=(C.c_int32 * n)(*[table_names.index(feats[i].table) for i in idxs]), dev=dev, stand_in=stand_in, bf16=bf16)
         if W == 1:
             g["inbox"], g["inbox_tag"], g["inbox_w"], g["recv2d"], g["ret"] = g["send"], g["send_tag"], g["send_w"], g["counts2d"], g["partial"]
         import os
@@ -897,9 +903,10 @@ class PreparedShardedForward:
             eng._a2a(g["inbox"], g["send"])
             eng._a2a(g["run"].view(-1), g["send_run"].view(-1))
             eng._a2a(g["inbox_w"], g["send_w"])
-        rc = lib.nrx_pool_inbox_fwd_runs(g["tp"], g["tr"], g["nt"], g["ft"], g["n"], g["B"], W, g["cap"], g["recv2d"].data_ptr(),
-                                         g["inbox"].data_ptr(), g["inbox_w"].data_ptr(), g["run"].data_ptr(), g["D"], g["partial"].data_ptr(),
-                                         None, stream)
+        pool = lib.nrx_pool_inbox_fwd_runs_bf16 if g.get("bf16") else lib.nrx_pool_inbox_fwd_runs
+        rc = pool(g["tp"], g["tr"], g["nt"], g["ft"], g["n"], g["B"], W, g["cap"], g["recv2d"].data_ptr(),
+                  g["inbox"].data_ptr(), g["inbox_w"].data_ptr(), g["run"].data_ptr(), g["D"], g["partial"].data_ptr(),
+                  None, stream)
         if rc:
             ops.check(rc, "nrx_pool_inbox_fwd_runs")
         if W > 1:
@@ -932,9 +939,10 @@ class PreparedShardedForward:
             eng._a2a(g["inbox"], g["send"])
             eng._a2a(g["inbox_tag"], g["send_tag"])
             eng._a2a(g["inbox_w"], g["send_w"])
-        rc = lib.nrx_pool_inbox_fwd(g["tp"], g["tr"], g["nt"], g["ft"], g["n"], g["B"], W, g["cap"], g["recv2d"].data_ptr(),
-                                    g["inbox"].data_ptr(), g["inbox_tag"].data_ptr(), g["inbox_w"].data_ptr(), g["D"],
-                                    g["partial"].data_ptr(), g["pws"].data_ptr(), None, stream)
+        pool = lib.nrx_pool_inbox_fwd_bf16 if g.get("bf16") else lib.nrx_pool_inbox_fwd
+        rc = pool(g["tp"], g["tr"], g["nt"], g["ft"], g["n"], g["B"], W, g["cap"], g["recv2d"].data_ptr(),
+                  g["inbox"].data_ptr(), g["inbox_tag"].data_ptr(), g["inbox_w"].data_ptr(), g["D"],
+                  g["partial"].data_ptr(), g["pws"].data_ptr(), None, stream)
         if rc:
             ops.check(rc, "nrx_pool_inbox_fwd")
         if W > 1:
@@ -1055,7 +1063,9 @@ def shard_model_(model, rank: int, world: int, group=None, backend=None):
     state_dict keys are unchanged; values are the local shards (use shard_table / unshard_tables to
     convert checkpoints: scatter-on-load / gather-on-save)."""
     import torch.nn as nn
-    ops.refuse_bf16_tables([e.weight for e in model.embedding_tables.values()], "shard_model_")
+    if any(e.weight.dtype is torch.bfloat16 for e in model.embedding_tables.values()):
+        raise NotImplementedError("shard_model_: bf16 embedding tables are not supported here -- its backward forms dense shard gradients, which "
+                                  "bf16 tables never have; the bound step trains them: shard_step.shard_model_step_(..., bf16_tables=True)")
     if getattr(model, "sparse_grad", False):
         # the routed backward delivers dense shard gradients; the row-sparse optimizers expect COO grads / the fused sink
         raise NotImplementedError("shard_model_: embeddings.sparse_grad is not supported together with row-sharded tables")
@@ -1096,7 +1106,8 @@ def full_state_dict(model, group=None) -> Dict[str, torch.Tensor]:
     """Gather-on-save for a model converted by shard_model_: the REFERENCE's state_dict -- `embedding_tables.<name>.weight` as the full
     [rows, D] table (base_model.py:531-536 loads it with strict=True), every other entry as it is (dense parameters are replicated) --
     on every rank.  One all-gather per sharded table (shards padded to the longest, rank 0's); a checkpoint written from it loads into the
-    reference, into the unsharded mirror, or back into any world size through load_full_state_dict_."""
+    reference, into the unsharded mirror, or back into any world size through load_full_state_dict_.  bf16 arenas
+    (shard_model_step_(bf16_tables=True)) come back as the full bf16 tables."""
     eng = getattr(model, "_shard_engine", None)
     world = eng.world if eng is not None else 1
     out: Dict[str, torch.Tensor] = {}
@@ -1115,8 +1126,13 @@ def full_state_dict(model, group=None) -> Dict[str, torch.Tensor]:
         pad = v.new_zeros((longest, v.shape[1]))
         lo = 1 if getattr(emb, "arena", False) else 0      # (shard_step.shard_model_step_: the local table is an arena with a leading dummy row)
         pad[:mine] = v.detach()[lo:lo + mine]
+        bits = pad.dtype is torch.bfloat16          # (gloo moves neither bf16 nor int16: the bit patterns travel as bytes)
+        if bits:
+            pad = pad.view(torch.uint8)
         parts = [torch.empty_like(pad) for _ in range(world)]
         dist.all_gather(parts, pad, group=group if group is not None else eng.group)
+        if bits:
+            parts = [p_.view(torch.bfloat16) for p_ in parts]
         out[k] = unshard_tables([p[:local_row_count(rows, r, world)] for r, p in enumerate(parts)])
     return out
 
@@ -1153,16 +1169,24 @@ class ShardedBenchPath:
     row-sharded over `world` ranks, B impressions per rank (weak scaling)."""
 
     def __init__(self, wl: str, device, seed: int, rank: int, world: int, batch: int, mode: str = "row", n_pool: int = 8,
-                 replicate_below_bytes: int = 256 << 20, host_staged: bool = False, engine: Optional[str] = None):
+                 replicate_below_bytes: int = 256 << 20, host_staged: bool = False, engine: Optional[str] = None,
+                 table_dtype: torch.dtype = torch.float32):
         """mode "row": every table row-sharded (the north-star layout).  mode "auto": planner -- tables
         of at most `replicate_below_bytes` are held in full on every rank (no exchange for them), larger
         ones are row-sharded.
         engine (default: NRX_SHARD_ENGINE, else "auto"): "feat" = shard_step.PreparedShardedStep (per-feature routing, the owner side is the
         single-GPU engine: bound forward AND bound row-sparse backward); "legacy" = PreparedShardedForward + the autograd training step;
-        "auto" = "feat" whenever a table is row-sharded."""
+        "auto" = "feat" whenever a table is row-sharded.
+        table_dtype: torch.bfloat16 draws the tables in bf16 (their own N(0, 1) stream; engine "feat" only) -- tools/bench_bf16_tables.py's
+        sharded leg and the full-size bf16 tests; bench.py's tables are fp32."""
         import os
         import bench
         feats, self.desc = bench.workload_spec(wl)
+        if table_dtype is not torch.float32:       # (refused before any table is drawn; the engine is resolved below as before)
+            want = engine or os.environ.get("NRX_SHARD_ENGINE", "auto")
+            sharded = mode != "auto" or any(f["rows"] * f["dim"] * 4 > replicate_below_bytes for f in feats)
+            if want not in ("feat", "auto") or (want == "auto" and not sharded):
+                raise NotImplementedError("ShardedBenchPath: bf16 tables run through the bound step only (engine 'feat')")
         self.rank, self.world, self.batch = rank, world, batch
         self.eng = RowShardedEmbedding(rank, world, overflow_policy="defer", host_staged=host_staged)
         gen = torch.Generator(device=device).manual_seed(seed)
@@ -1179,10 +1203,10 @@ class ShardedBenchPath:
                 rep_of[tname] = rep
                 nrows = f["rows"] if rep else local_row_count(f["rows"], rank, world)
                 if rep:      # identical replica on every rank
-                    t = torch.empty((nrows, f["dim"]), dtype=torch.float32, device=device)
+                    t = torch.empty((nrows, f["dim"]), dtype=table_dtype, device=device)
                     t.normal_(generator=torch.Generator(device=device).manual_seed(seed - rank + len(self.tables)))
                 else:        # the shard is rows 1.. of an arena whose row 0 is the dummy row the bound step's owner ids name with 0
-                    arena = torch.empty((nrows + 1, f["dim"]), dtype=torch.float32, device=device)
+                    arena = torch.empty((nrows + 1, f["dim"]), dtype=table_dtype, device=device)
                     arena[0].zero_()
                     t = arena[1:]
                     t.normal_(generator=gen)
@@ -1216,6 +1240,8 @@ class ShardedBenchPath:
         if engine == "auto":
             engine = "feat" if self.n_sharded > 0 else "legacy"
         self.engine = engine
+        if table_dtype is not torch.float32 and engine != "feat":
+            raise NotImplementedError("ShardedBenchPath: bf16 tables run through the bound step only (engine 'feat')")
         if engine == "feat":
             from .shard_step import PreparedShardedStep
             tabs = {n: self.arenas.get(n, t) for n, t in self.tables.items()}

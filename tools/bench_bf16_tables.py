@@ -12,6 +12,18 @@ table ([rows, 2, D]); where they do not fit next to the tables (C5; C3 on a box 
 
     python tools/bench_bf16_tables.py [--workloads c2,c3,c4,c5] [--iters 50] [--train-iters 20] [--out profiles/bf16_tables_lines.jsonl]
     python tools/bench_bf16_tables.py --workloads c2 --dtypes bf16 --legs fwd      # the form profiled under rocprofv3
+
+--sharded: the BOUND SHARDED STEP at world 1 instead (shard_step.PreparedShardedStep over sharding.ShardedBenchPath's tables, the path bench.py's
+sharded legs time), per workload:
+  sharded_fwd    the bound forward (the forward-only calls of the path, cycling over its id sets)
+  sharded_step   forward + backward + FusedSparseAdam on the arenas (bf16: row maps wired, nrx_sparse_adam_step_bf16_rows) -- or, where the
+                 fp32 moments of every row do not fit (C5), `sharded_fwd_bwd`: the same without the optimizer
+Both storage types are built and warmed up, then timed ALTERNATING, `--rounds` times each, so a drift of the device shows in both; every
+round's time is kept and the fp32 leg's own spread stands beside every ratio.  Where the two table sets do not fit together (C5: 224 + 112 GB)
+they run one after the other (`alternating: false`).  `allocated_bytes` = torch.cuda.memory_allocated() after the tables are built.
+
+    python tools/bench_bf16_tables.py --sharded [--workloads c2,c3,c4,c5] [--rounds 3] [--out profiles/bf16_sharded_lines.jsonl]
+    python tools/bench_bf16_tables.py --sharded --workloads c4 --dtypes bf16 --rounds 1      # the form profiled under rocprofv3
 """
 import argparse
 import json
@@ -161,6 +173,94 @@ def run_workload(wl, dtype, legs, iters, train_iters, dev):
     return out
 
 
+class ShardedLegs:
+    """One storage type of one workload through the bound sharded step at world 1."""
+
+    def __init__(self, wl, dtype, dev, with_opt):
+        from news_recsys_amd.shard_step import arena_row_map
+        from news_recsys_amd.sharding import ShardedBenchPath
+        base = torch.cuda.memory_allocated(dev)
+        self.path = ShardedBenchPath(wl, dev, 0, 0, 1, B, "row", table_dtype=dtype)
+        torch.cuda.synchronize()
+        self.allocated = torch.cuda.memory_allocated(dev) - base
+        self.table_bytes = sum(a.numel() * a.element_size() for a in self.path.arenas.values())
+        assert self.path.train_setup()
+        self.with_opt = with_opt
+        self.i = 0
+        self.sink = self.opt = None
+        if with_opt:
+            names = sorted(self.path.arenas)
+            params = [self.path.arenas[n] for n in names]
+            self.sink = ops.SparseGradSink()
+            self.opt = FusedSparseAdam(self.sink, lr=1e-3, params=params, sr_seed=1,
+                                       row_maps=[arena_row_map(0, 1)] * len(params) if dtype is torch.bfloat16 else None)
+
+    def fwd(self):
+        calls = self.path.calls
+        self.i += 1
+        calls[2 + self.i % (len(calls) - 2)].run()
+
+    def step(self):
+        self.i += 1
+        entries = self.path.train_step(self.i)
+        if self.opt is not None:
+            self.sink.pending.extend(entries)
+            self.opt.step()
+
+
+def run_sharded(wl, dtypes, rounds, iters, train_iters, dev):
+    feats, _ = workload_spec(wl)
+    fp32_bytes = sum(f["rows"] * f["dim"] * 4 for f in feats if "share" not in f)
+    free, _ = torch.cuda.mem_get_info(dev)
+    with_opt = 3 * fp32_bytes < 0.8 * free                   # one storage type's tables + fp32 moments [rows, 2, D]
+    together = len(dtypes) > 1 and (5.5 if with_opt else 1.5) * fp32_bytes < 0.8 * free
+    step_leg = "sharded_step" if with_opt else "sharded_fwd_bwd"
+    times = {(dn, leg): [] for dn in dtypes for leg in ("sharded_fwd", step_leg)}
+    info = {}
+
+    def build(dn):
+        s = ShardedLegs(wl, {"fp32": torch.float32, "bf16": torch.bfloat16}[dn], dev, with_opt)
+        info[dn] = dict(allocated_bytes=int(s.allocated), table_bytes=int(s.table_bytes))
+        timed(s.fwd, 5, warm=5)
+        timed(s.step, 3, warm=3)
+        return s
+
+    def measure(dn, s):
+        times[(dn, "sharded_fwd")].append(timed(s.fwd, iters, warm=2))
+        times[(dn, step_leg)].append(timed(s.step, train_iters, warm=2))
+
+    if together:
+        legs = {dn: build(dn) for dn in dtypes}
+        for _ in range(rounds):
+            for dn in dtypes:
+                measure(dn, legs[dn])
+        del legs
+    else:
+        for dn in dtypes:
+            s = build(dn)
+            for _ in range(rounds):
+                measure(dn, s)
+            del s
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    out = []
+    med = {}
+    for (dn, leg), ms in times.items():
+        srt = sorted(ms)
+        med[(dn, leg)] = srt[len(srt) // 2]
+        out.append(dict(workload=wl, table_dtype=dn, leg=leg, world=1, batch=B, ms_rounds=[round(x, 5) for x in ms], ms_median=round(med[(dn, leg)], 5),
+                        spread_over_median=round((srt[-1] - srt[0]) / med[(dn, leg)], 4), alternating=bool(together),
+                        optimizer=bool(with_opt), **info[dn]))
+    if "fp32" in dtypes and "bf16" in dtypes:
+        for leg in ("sharded_fwd", step_leg):
+            f32 = sorted(times[("fp32", leg)])
+            out.append(dict(workload=wl, leg=leg, bf16_over_fp32_time=round(med[("bf16", leg)] / med[("fp32", leg)], 4),
+                            fp32_spread_over_median=round((f32[-1] - f32[0]) / med[("fp32", leg)], 4), alternating=bool(together)))
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="c2,c3,c4,c5")
@@ -169,8 +269,21 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--train-iters", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sharded", action="store_true", help="the bound sharded step at world 1 (see the module docstring)")
+    ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args(argv)
     dev = torch.device("cuda:0")
+    if a.sharded:
+        lines = []
+        for wl in a.workloads.split(","):
+            for ln in run_sharded(wl, a.dtypes.split(","), a.rounds, a.iters, a.train_iters, dev):
+                lines.append(ln)
+                print(json.dumps(ln), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                for ln in lines:
+                    f.write(json.dumps(ln) + "\n")
+        return
     dts = {"fp32": torch.float32, "bf16": torch.bfloat16}
     legs = set(a.legs.split(","))
     lines = []

@@ -289,9 +289,9 @@ NRX_API int nrx_sparse_plan_stats(const int64_t* counts, const int64_t* n_walk, 
  * two upstream rows of a record and stores 0 + first + second, the sum the sorted walk forms for a two-entry segment, bit for bit.
  * Every feature must be NRX_SPARSE and named in place_feats; workspace as nrx_embed_bwd_placed (required).
  * NRX_ERR_UNSUPPORTED (nothing enqueued) outside the placement pass's shapes (dim 16 / 32 / 64, 16-byte-aligned operands).
- * aux_stream (optional, another stream of the same device; a measurement knob -- on C2 the overlap LOSES 11 us, profiles/r05_pairs_aux.txt): the
- * pair pass, the walk and the work lists are enqueued THERE, behind what `stream` holds at the call, and the placement pass on `stream`, which
- * then waits for aux_stream.  NULL: everything on `stream`, one launch after the other. */
+ * aux_stream is reserved: pass NULL (or `stream`); anything else is NRX_ERR_BAD_ARG.  Every launch goes to `stream`, one after the other.  (The
+ * parameter once put the pair pass, the walk and the work lists on a second stream next to the placement pass: on C2 the overlap LOST 11 us,
+ * profiles/r05_pairs_aux.txt.) */
 NRX_API int nrx_embed_bwd_placed_pairs(const nrx_feature_t* feats, int32_t n_feats, int64_t batch, int32_t dim,
                                const float* g_out, int64_t out_ld, const float* g_wide, int64_t wide_ld,
                                const int64_t* order, const int64_t* seg_start, const int64_t* uniq_keys,

@@ -3437,34 +3437,52 @@ extern "C" int64_t nrx_embed_bwd_sorted_workspace(int64_t n_lookups, int32_t dim
            2 * (n_lookups * 4 + 64) + n_lookups / 8 + 128;       // + bag features: per-lookup scale, per-sample factor, weight bits
 }
 
-static int embed_bwd_sorted_impl(const nrx_feature_t* feats, int32_t n_feats, int64_t batch, int32_t dim,
-                                 const float* g_out, int64_t out_ld, const float* g_wide, int64_t wide_ld,
-                                 const int64_t* order, const int64_t* seg_start, const int64_t* uniq_keys,
-                                 int64_t n_unique, const int64_t* n_unique_dev, const nrx_fm_grad_t* fm, float* values,
-                                 uint64_t place_feats, const int32_t* dest, const int32_t* walk, const int64_t* n_walk,
-                                 void* workspace, int64_t ws_bytes /* 0: the size nrx_embed_bwd_sorted_workspace promises */, void* stream,
-                                 float* const* grad_tables = nullptr, int32_t n_tables = 0, int32_t add_to = 0,
-                                 bool pairs = false /* the plan is nrx_sparse_plan_lds's: rows looked up twice are finished by embed_bwd_pairs_kernel */,
-                                 void* aux_stream = nullptr /* pairs: the pair pass, the walk and the work lists run THERE, next to the placement pass */,
-                                 const int32_t* pair_recs = nullptr, const int64_t* n_pairs = nullptr,
-                                 bool place_only = false /* nrx_embed_bwd_scatter: the placement pass alone (dest is the caller's) */,
-                                 float* const* multi_bases = nullptr, int multi_n = 0, int multi_shift = 0 /* place_only into several buffers */,
-                                 bool skip_place = false /* nrx_embed_bwd_walk: the placed rows are in values already (written by the requesters) */) {
-    NRX_REQUIRE(feats != nullptr && n_feats >= 1 && n_feats <= NRX_MAX_FEATURES,
-                "nrx_embed_bwd_sorted: n_feats must be in [1, %d]", NRX_MAX_FEATURES);
-    NRX_REQUIRE(batch >= 0 && dim >= 1 && n_unique >= 0, "nrx_embed_bwd_sorted: bad argument");
-    const bool has_fm = fm != nullptr && fm->g_fm != nullptr;
-    NRX_REQUIRE(g_out != nullptr || g_wide != nullptr || has_fm, "nrx_embed_bwd_sorted: no upstream gradient");
-    if (n_unique == 0 || batch == 0) return NRX_OK;
-    const bool dense = grad_tables != nullptr;
-    NRX_REQUIRE(order && seg_start && (values || dense), "nrx_embed_bwd_sorted: null buffer");
-    NRX_REQUIRE(!dense || (uniq_keys != nullptr && n_tables >= 1 && n_tables <= NRX_MAX_FEATURES),
+// ---- the host side of the sorted backward: an entry point fills a SortedBwdCall; embed_bwd_sorted_impl packs it, classifies its shape, runs the launches
+enum SortedBwdMode {
+    SORTED_BWD_ALL = 0,         // the placement pass (when dest is given), the walk, the work lists
+    SORTED_BWD_PAIRS,           // the plan is nrx_sparse_plan_lds's: rows looked up twice are finished by embed_bwd_pairs_kernel
+    SORTED_BWD_PLACE_ONLY,      // nrx_embed_bwd_scatter: the placement pass alone (dest is the caller's)
+    SORTED_BWD_SKIP_PLACE,      // nrx_embed_bwd_walk: the placed rows are in values already (written by the requesters); pair records optional
+};
+
+struct SortedBwdCall {
+    const nrx_feature_t* feats = nullptr; int32_t n_feats = 0; int64_t batch = 0; int32_t dim = 0;
+    const float* g_out = nullptr; int64_t out_ld = 0; const float* g_wide = nullptr; int64_t wide_ld = 0;
+    const int64_t* order = nullptr; const int64_t* seg_start = nullptr; const int64_t* uniq_keys = nullptr;
+    int64_t n_unique = 0; const int64_t* n_unique_dev = nullptr; const nrx_fm_grad_t* fm = nullptr; float* values = nullptr;
+    uint64_t place_feats = 0; const int32_t* dest = nullptr; const int32_t* walk = nullptr; const int64_t* n_walk = nullptr;
+    void* workspace = nullptr; int64_t ws_bytes = 0 /* 0: the size nrx_embed_bwd_sorted_workspace promises */; void* stream = nullptr;
+    float* const* grad_tables = nullptr; int32_t n_tables = 0; int32_t add_to = 0;
+    SortedBwdMode mode = SORTED_BWD_ALL;
+    const int32_t* pair_recs = nullptr; const int64_t* n_pairs = nullptr;
+    float* const* multi_bases = nullptr; int multi_n = 0; int multi_shift = 0 /* SORTED_BWD_PLACE_ONLY into several buffers */;
+    bool dense() const { return grad_tables != nullptr; }
+    bool pairs() const { return mode == SORTED_BWD_PAIRS || (mode == SORTED_BWD_SKIP_PLACE && pair_recs != nullptr); }
+};
+
+// What the launch tables branch on, computed once per call (sorted_bwd_classify).
+struct SortedBwdShape {
+    int ql, long_t;
+    bool has_fm, fast, unal, has_bag, placed;
+    bool bag_shape;             // bag launches: 2 rows x 4 entries per pass (see the kernel)
+    bool reg;                   // arithmetic decode (embed_bwd_sorted_fast_kernel<.., DEC = 1>)
+    bool few;                   // scalar decode (DEC = 2); else the LDS table (DEC = 0)
+};
+
+// Stage 1: the request checked and packed into the kernels' argument block.  grads_al: every dense gradient table is 16-byte aligned.
+static int sorted_bwd_pack(const SortedBwdCall& c, SortedBwdArgs& a, bool& grads_al) {
+    const nrx_feature_t* feats = c.feats;
+    const nrx_fm_grad_t* fm = c.fm;
+    const int32_t n_feats = c.n_feats, dim = c.dim;
+    const int64_t batch = c.batch;
+    const bool has_fm = fm != nullptr && fm->g_fm != nullptr, dense = c.dense();
+    NRX_REQUIRE(c.order && c.seg_start && (c.values || dense), "nrx_embed_bwd_sorted: null buffer");
+    NRX_REQUIRE(!dense || (c.uniq_keys != nullptr && c.n_tables >= 1 && c.n_tables <= NRX_MAX_FEATURES),
                 "nrx_embed_bwd_placed_dense: needs uniq_keys and 1 .. %d tables", NRX_MAX_FEATURES);
     {
         int rc = check_fm_grad(fm, feats, n_feats, "nrx_embed_bwd_sorted");
         if (rc != NRX_OK) return rc;
     }
-    SortedBwdArgs a;
     a.g_fm = has_fm ? fm->g_fm : nullptr;
     a.fm_sums = has_fm ? fm->fm_sums : nullptr;
     a.sums_ld = has_fm ? fm->sums_ld : 0;
@@ -3479,7 +3497,7 @@ static int embed_bwd_sorted_impl(const nrx_feature_t* feats, int32_t n_feats, in
     a.n_walk_dev = nullptr;
     a.gs_all = nullptr;
     a.long_t = SORTED_LONG_T;
-    a.dense = dense ? (add_to ? 2 : 1) : 0;
+    a.dense = dense ? (c.add_to ? 2 : 1) : 0;
     for (int i = 0; i < NRX_MAX_FEATURES; ++i) a.f[i].index = nullptr;
     int64_t off = 0;
     for (int i = 0; i < n_feats; ++i) {
@@ -3510,12 +3528,12 @@ static int embed_bwd_sorted_impl(const nrx_feature_t* feats, int32_t n_feats, in
         off += batch * (s.kind == NRX_SPARSE ? 1 : s.bag_len);
     }
     a.off[n_feats] = off;
-    bool grads_al = true;
+    grads_al = true;
     if (dense) {                       // slot t of the descriptor array carries table t's gradient base (see SortedBwdArgs::dense)
-        for (int t = 0; t < n_tables; ++t) {
-            NRX_REQUIRE(grad_tables[t] != nullptr, "nrx_embed_bwd_placed_dense: table %d: null gradient pointer", t);
-            a.f[t].index = grad_tables[t];
-            grads_al = grads_al && nrx_aligned16(grad_tables[t]);
+        for (int t = 0; t < c.n_tables; ++t) {
+            NRX_REQUIRE(c.grad_tables[t] != nullptr, "nrx_embed_bwd_placed_dense: table %d: null gradient pointer", t);
+            a.f[t].index = c.grad_tables[t];
+            grads_al = grads_al && nrx_aligned16(c.grad_tables[t]);
         }
         for (int i = 0; i < n_feats; ++i)
             NRX_REQUIRE(feats[i].table != nullptr, "nrx_embed_bwd_placed_dense: feature %d: feats[i].table must be its table's gradient", i);
@@ -3532,29 +3550,30 @@ static int embed_bwd_sorted_impl(const nrx_feature_t* feats, int32_t n_feats, in
     for (int i = 0; i < n_feats && a.regular; ++i)
         a.regular = feats[i].kind == NRX_SPARSE && feats[i].wide_col < 0 && feats[i].out_col == a.col0 + i * a.col_stride &&
                     a.f[i].fm == a.f[0].fm;
-    a.batch = batch;
-    a.g_out = g_out;
-    a.out_ld = out_ld;
-    a.g_wide = g_wide;
-    a.wide_ld = wide_ld;
-    a.order = order;
-    a.seg_start = seg_start;
-    a.uniq_keys = uniq_keys;
-    a.n_unique = n_unique;
-    a.n_unique_dev = n_unique_dev;
-    a.values = values;
-    a.n = n_feats;
-    a.dim = dim;
+    a.batch = batch; a.n = n_feats; a.dim = dim;
+    a.g_out = c.g_out; a.out_ld = c.out_ld; a.g_wide = c.g_wide; a.wide_ld = c.wide_ld;
+    a.order = c.order; a.seg_start = c.seg_start; a.uniq_keys = c.uniq_keys; a.n_unique = c.n_unique; a.n_unique_dev = c.n_unique_dev;
+    a.values = c.values;
+    return NRX_OK;
+}
+
+// Stage 2: which kernels the launch can take.
+static SortedBwdShape sorted_bwd_classify(const SortedBwdCall& c, const SortedBwdArgs& a, bool grads_al) {
+    const nrx_feature_t* feats = c.feats;
+    const nrx_fm_grad_t* fm = c.fm;
+    const float* g_out = c.g_out;
+    const int32_t n_feats = c.n_feats, dim = c.dim;
+    const int64_t off = a.off[n_feats];
+    const bool has_fm = fm != nullptr && fm->g_fm != nullptr;
+    int long_t = SORTED_LONG_T;
     int ql = ceil_log2((dim + 3) / 4);
     if (ql > 6) ql = 6;
-    const int tb = NRX_BLOCK >> ql;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     // fast form: plain single-valued features, D = 4 Q exactly, float4-addressable everywhere
-    bool fast = dim == (4 << ql) && ql >= 2 && ql <= 4 && (dense ? grads_al : nrx_aligned16(values)) &&
+    bool fast = dim == (4 << ql) && ql >= 2 && ql <= 4 && (c.dense() ? grads_al : nrx_aligned16(c.values)) &&
                 (!has_fm || (nrx_aligned16(fm->feat) && (fm->feat_ld & 3) == 0 && nrx_aligned16(fm->fm_sums) &&
                              (fm->sums_ld & 3) == 0 && fm->sums_ld >= dim));
     bool has_bag = false;
-    bool unal = !(g_out == nullptr || (nrx_aligned16(g_out) && (out_ld & 3) == 0));      // wide routing / shifted columns / odd strides
+    bool unal = !(g_out == nullptr || (nrx_aligned16(g_out) && (c.out_ld & 3) == 0));      // wide routing / shifted columns / odd strides
     for (int i = 0; i < n_feats && fast; ++i) {
         unal |= feats[i].wide_col >= 0 || (feats[i].out_col & 3) != 0;
         if (feats[i].wide_col >= 0) fast = feats[i].kind == NRX_SPARSE;                 // (the split is defined for single-valued features)
@@ -3563,142 +3582,103 @@ static int embed_bwd_sorted_impl(const nrx_feature_t* feats, int32_t n_feats, in
     if (unal) fast = fast && !has_fm && (reinterpret_cast<uintptr_t>(g_out) & 3u) == 0;
     // bag features ride the fast form through a per-lookup scale array that lives in the workspace; FM fields are
     // single-valued by construction (fm/model.py:48-59 stacks [B, D] tensors)
-    if (has_bag) fast = fast && workspace != nullptr && !has_fm && off < 0xffffffffLL;
+    if (has_bag) fast = fast && c.workspace != nullptr && !has_fm && off < 0xffffffffLL;
     // threshold sweep (T = 16 / 24 / 32 / 48 / 64, fwd+bwd us): C4 521 / 505 / 493 / 492 / 492, C4 Zipf 581 / 575 / 564 / 598 / 674,
     // C2 Zipf 501 / 545 / 588 / 678 / 758, C5 478 / 491 / 527 / 578 / 618: bag launches (a few rows, each looked up ~L times) take 32
-    if (has_bag) a.long_t = 2 * SORTED_LONG_T;
+    if (has_bag) long_t = 2 * SORTED_LONG_T;
     // NRX_FEAT_MANY_PER_ROW (the sharded step's pooled channel: a bag feature's lookups arrive at the owner as ONE single-valued pseudo-feature, ~16
     // lookups per row of the pooled table): the row statistics of a bag launch, hence its threshold (16 -> 32: the walk 110 -> 68 us, the work lists
     // 103 -> 5 us on C4's pseudo-batch).  A flag of the CALLER, not a guess from the table sizes: the threshold decides which rows leave the
     // in-order walk for the tree-summed work lists, so two call paths of one launch must agree on it to produce the same bits (a heuristic on
     // feats[].rows -- which the row-sparse and the dense entry points fill differently -- broke exactly that: tests/stress_embed_bwd.py).
     for (int i = 0; i < n_feats; ++i)
-        if (!has_bag && (feats[i].flags & NRX_FEAT_MANY_PER_ROW)) a.long_t = 2 * SORTED_LONG_T;
-    if (const char* e = getenv("NRX_LONG_T")) { const int v = atoi(e); if (v >= 2 && v <= 256) a.long_t = v; }      // measurement knob
+        if (!has_bag && (feats[i].flags & NRX_FEAT_MANY_PER_ROW)) long_t = 2 * SORTED_LONG_T;
+    if (const char* e = getenv("NRX_LONG_T")) { const int v = atoi(e); if (v >= 2 && v <= 256) long_t = v; }      // measurement knob
+    SortedBwdShape s;
+    s.ql = ql; s.long_t = long_t; s.has_fm = has_fm; s.fast = fast; s.unal = unal; s.has_bag = has_bag;
     // placement mode: single-lookup rows are stored by the placement pass, the walk reduces the listed rows only
-    const bool placed = fast && dest != nullptr;
-    if (pairs && !(placed && !has_bag)) {
+    s.placed = fast && c.dest != nullptr;
+    s.bag_shape = has_bag && !unal && !has_fm;
+    s.reg = a.regular && (g_out != nullptr || has_fm) && !unal;
+    s.few = n_feats <= 4;
+    return s;
+}
+
+// The shapes each caller mode takes.  NRX_ERR_UNSUPPORTED comes before anything is enqueued: the one-call entries fall back on it.
+static int sorted_bwd_check_mode(const SortedBwdCall& c, const SortedBwdShape& s) {
+    const bool place_shape = s.placed && !s.has_bag;
+    if (c.pairs() && !place_shape) {
         nrx_set_error("nrx_embed_bwd_placed_pairs: the launch is outside the placement pass's shapes (dim 16 / 32 / 64, aligned operands, single-valued features)");
         return NRX_ERR_UNSUPPORTED;
     }
-    if (skip_place && !(placed && !has_bag)) {
+    if (c.mode == SORTED_BWD_SKIP_PLACE && !place_shape) {
         nrx_set_error("nrx_embed_bwd_walk: the launch is outside the placement plan's shapes (dim 16 / 32 / 64, aligned operands, single-valued features)");
         return NRX_ERR_UNSUPPORTED;
     }
-    if (place_only && multi_bases != nullptr && unal) {
+    if (c.mode == SORTED_BWD_PLACE_ONLY && c.multi_bases != nullptr && s.unal) {
         nrx_set_error("nrx_embed_bwd_scatter_multi: aligned upstream rows only");
         return NRX_ERR_UNSUPPORTED;
     }
-    if (place_only && !(placed && !has_bag)) {
+    if (c.mode == SORTED_BWD_PLACE_ONLY && !place_shape) {
         nrx_set_error("nrx_embed_bwd_scatter: the launch is outside the placement pass's shapes (dim 16 / 32 / 64, aligned operands, single-valued features)");
         return NRX_ERR_UNSUPPORTED;
     }
-    if (fast) {
-        constexpr int R = 4;
-        constexpr int RB = 2;                   // bag launches: 2 rows x 4 entries per pass (see the kernel)
-        const bool bag_shape = has_bag && !unal && !has_fm;
-        const bool wide_pass = bag_shape || placed;       // placement mode: every walked row has >= 2 entries -> 2 rows x 4 entries too
-        int64_t n_rows = n_unique;                        // rows of the walk launch (upper bound when the count lives on the device)
-        int n_place = 0;
-        PlaceArgs pa;
-        if (placed) {
-            int64_t placeable = 0;
-            for (int i = 0; i < n_feats; ++i) {
-                if (!((place_feats >> i) & 1ull)) continue;
-                NRX_REQUIRE(feats[i].kind == NRX_SPARSE, "nrx_embed_bwd_placed: feature %d is not single-valued: it cannot be placed", i);
-                pa.off[n_place] = a.off[i];
-                pa.ids[n_place] = feats[i].index;
-                pa.grad[n_place] = const_cast<float*>(feats[i].table);
-                NRX_REQUIRE(!dense || (feats[i].index != nullptr && (feats[i].index_bits == 32 || feats[i].index_bits == 64) &&
-                                       feats[i].index_bits == feats[0].index_bits),
-                            "nrx_embed_bwd_placed_dense: feature %d: the placement pass reads the ids (one width per launch)", i);
-                pa.out_col[n_place] = feats[i].out_col;
-                pa.wide_col[n_place] = feats[i].wide_col;
-                pa.fm[n_place] = a.f[i].fm;
-                placeable += batch;
-                ++n_place;
-            }
-            // walked rows: >= 2 lookups each, or one lookup of a feature outside the mask, or a table's padding row
-            const int64_t bound = placeable / 2 + (off - placeable) + n_feats + 1;
-            if (bound < n_rows) n_rows = bound;
-            a.walk = walk;
-            a.n_walk_dev = n_walk;
-            a.n_unique = n_rows;
-        }
-        const int64_t groups = (n_rows + (wide_pass ? RB : R) - 1) / (wide_pass ? RB : R);
-        unsigned grid = (unsigned)((groups + tb - 1) / tb);
-        {   // the walk's blocks stride over the row groups: when the row count is a device-side number (n_rows is only its bound) a few rounds of resident blocks are enough
-            static const int cap = getenv("NRX_WALK_GRID") ? atoi(getenv("NRX_WALK_GRID")) : 4096;
-            if ((n_unique_dev != nullptr || placed) && cap > 0 && grid > (unsigned)cap) grid = (unsigned)cap;
-            if (pairs && grid > 512u) grid = 512u;      // (only the rows looked up 3+ times are walked: a few per thousand lookups on near-unique ids)
-        }
-        // (4 rows x 4 entries per lane group instead of 2 x 4: C5 446.9 -> 458.1 us, C3 163.2 -> 169.6 -- measured, not kept)
-        if (workspace != nullptr) {        // long segments (hot rows) go through the wavefront-per-item path
-            a.long_ws = reinterpret_cast<int32_t*>((reinterpret_cast<uintptr_t>(workspace) + 15) & ~(uintptr_t)15);
-            a.long_items_cap = off / SORTED_LONG_T + 8;
-            a.long_slots_cap = sorted_long_slots_cap(off);
-            // the four work-list counters are cleared by a kernel (nrx_zero_async), not hipMemsetAsync: inside a captured HIP graph
-            // the 16-byte memset node did not take effect on replay (counters kept growing, the list was read past what was written)
-            // (placement mode: the placement pass clears them -- one launch less)
-            // (launches with bag features: cleared together with the weight-bit words below -- one launch, not two)
-            if ((!(placed && n_place > 0) || skip_place) && !has_bag && nrx_zero_async(a.long_ws, 16, st) != NRX_OK) return NRX_ERR_LAUNCH;
-            const bool side_zero = pairs && placed && n_place > 0 && aux_stream != nullptr && aux_stream != stream;      // (side-stream mode: the placement pass
-            if (side_zero && nrx_zero_async(a.long_ws, 16, reinterpret_cast<hipStream_t>(aux_stream)) != NRX_OK) return NRX_ERR_LAUNCH;      //  runs elsewhere: the counters are cleared on the walk's stream)
-        }
-        const bool side_mode = pairs && aux_stream != nullptr && aux_stream != stream;
-        auto launch_place = [&]() {
-        if (placed && n_place > 0 && !skip_place) {
-            pa.batch = batch;
-            pa.g_out = g_out; pa.out_ld = out_ld; pa.g_wide = g_wide; pa.wide_ld = wide_ld;
-            pa.g_fm = a.g_fm; pa.fm_sums = a.fm_sums; pa.sums_ld = a.sums_ld; pa.feat = a.feat; pa.feat_ld = a.feat_ld;
-            pa.dest = dest;
-            pa.values = values;
-            pa.idx64 = feats[0].index_bits == 64;
-            pa.add_to = add_to ? 1 : 0;
-            { const char* e = getenv("NRX_PLACE_STNT"); pa.stnt = e ? atoi(e) : 0; }
-            pa.long_ws = side_mode ? nullptr : a.long_ws;
-            pa.n = n_place;
-            { const char* e = getenv("NRX_PLACE_NT"); pa.nt = e ? atoi(e) : 1; }
-            const int uvar = getenv("NRX_PLACE_U") ? atoi(getenv("NRX_PLACE_U")) : 4;       // fetches in flight per lane (4 | 8)
-            // full-line form (embed_bwd_place_lines_kernel): 64-byte rows whose feature pairs (2j, 2j + 1) are one aligned 128-byte line of the
-            // upstream rows (and of the forward concat); NRX_PLACE_LINES=0 keeps the one-feature-per-lane-group form
-            bool lines = ql == 2 && !unal && pa.nt != 0 && pa.stnt == 0 && (g_out != nullptr || has_fm) && (reinterpret_cast<uintptr_t>(g_out) & 127) == 0 &&
-                         (g_out == nullptr || (out_ld & 31) == 0) && n_place <= 64;
-            if (lines && has_fm) lines = (reinterpret_cast<uintptr_t>(pa.feat) & 127) == 0 && (pa.feat_ld & 31) == 0;
-            pa.fm_mask = 0;
-            for (int i = 0; i < n_place; ++i) {
-                if (pa.fm[i]) pa.fm_mask |= 1ull << i;
-                if (pa.wide_col[i] >= 0) lines = false;
-                if ((i & 1) == 0 ? (pa.out_col[i] & 31) != 0 : pa.out_col[i] != pa.out_col[i - 1] + 16) lines = false;
-            }
-            { const char* e = getenv("NRX_PLACE_LINES"); if (e && atoi(e) == 0) lines = false; }
-            pa.multi_shift = 0;
-            if (multi_bases != nullptr) {      // several destination buffers: the one-feature-per-lane-group form carries the base table (in grad[])
-                for (int i = 0; i < multi_n; ++i) pa.grad[i] = multi_bases[i];
-                pa.multi_shift = multi_shift;
-                const unsigned pgrid = (unsigned)((batch + tb - 1) / tb);
-                const size_t plds = (size_t)n_place * tb * 4;
-                if (ql == 2) { if (has_fm) hipLaunchKernelGGL((embed_bwd_place_kernel<2, 4, true, false, false, true>), dim3(pgrid), dim3(NRX_BLOCK), plds, st, pa);
-                               else hipLaunchKernelGGL((embed_bwd_place_kernel<2, 4, false, false, false, true>), dim3(pgrid), dim3(NRX_BLOCK), plds, st, pa); }
-                else if (ql == 3) { if (has_fm) hipLaunchKernelGGL((embed_bwd_place_kernel<3, 4, true, false, false, true>), dim3(pgrid), dim3(NRX_BLOCK), plds, st, pa);
-                                    else hipLaunchKernelGGL((embed_bwd_place_kernel<3, 4, false, false, false, true>), dim3(pgrid), dim3(NRX_BLOCK), plds, st, pa); }
-                else { if (has_fm) hipLaunchKernelGGL((embed_bwd_place_kernel<4, 4, true, false, false, true>), dim3(pgrid), dim3(NRX_BLOCK), plds, st, pa);
-                       else hipLaunchKernelGGL((embed_bwd_place_kernel<4, 4, false, false, false, true>), dim3(pgrid), dim3(NRX_BLOCK), plds, st, pa); }
-                return;
-            }
-            if (lines) {
-                const unsigned lgrid = (unsigned)((batch + 31) / 32);
-                const size_t llds = (size_t)n_place * PLACE_LINES_TBP * 4;
-                if (g_out == nullptr && dense) hipLaunchKernelGGL((embed_bwd_place_lines_kernel<NRX_LINES_U, true, true, false>), dim3(lgrid), dim3(NRX_BLOCK), llds, st, pa);
-                else if (g_out == nullptr) hipLaunchKernelGGL((embed_bwd_place_lines_kernel<NRX_LINES_U, true, false, false>), dim3(lgrid), dim3(NRX_BLOCK), llds, st, pa);
-                else if (dense && has_fm) hipLaunchKernelGGL((embed_bwd_place_lines_kernel<NRX_LINES_U, true, true>), dim3(lgrid), dim3(NRX_BLOCK), llds, st, pa);
-                else if (dense) hipLaunchKernelGGL((embed_bwd_place_lines_kernel<NRX_LINES_U, false, true>), dim3(lgrid), dim3(NRX_BLOCK), llds, st, pa);
-                else if (has_fm) hipLaunchKernelGGL((embed_bwd_place_lines_kernel<NRX_LINES_U, true, false>), dim3(lgrid), dim3(NRX_BLOCK), llds, st, pa);
-                else hipLaunchKernelGGL((embed_bwd_place_lines_kernel<NRX_LINES_U, false, false>), dim3(lgrid), dim3(NRX_BLOCK), llds, st, pa);
-            } else {
-            const unsigned pgrid = (unsigned)((batch + tb - 1) / tb);
-            const size_t plds = (size_t)n_place * tb * 4;
-            constexpr int U = 8;
+    return NRX_OK;
+}
+
+// The placement pass: the `lines`, multi_bases and one-feature-per-lane-group forms.
+static void sorted_bwd_launch_place(const SortedBwdCall& c, const SortedBwdShape& s, const SortedBwdArgs& a, PlaceArgs& pa, int n_place, hipStream_t st) {
+    const int64_t batch = c.batch, out_ld = c.out_ld;
+    const float* g_out = c.g_out;
+    const int ql = s.ql, tb = NRX_BLOCK >> ql;
+    const bool dense = c.dense(), has_fm = s.has_fm, unal = s.unal;
+    pa.batch = batch; pa.g_out = g_out; pa.out_ld = out_ld; pa.g_wide = c.g_wide; pa.wide_ld = c.wide_ld;
+    pa.g_fm = a.g_fm; pa.fm_sums = a.fm_sums; pa.sums_ld = a.sums_ld; pa.feat = a.feat; pa.feat_ld = a.feat_ld;
+    pa.dest = c.dest; pa.values = c.values; pa.idx64 = c.feats[0].index_bits == 64; pa.add_to = c.add_to ? 1 : 0;
+    { const char* e = getenv("NRX_PLACE_STNT"); pa.stnt = e ? atoi(e) : 0; }
+    pa.long_ws = a.long_ws;
+    pa.n = n_place;
+    { const char* e = getenv("NRX_PLACE_NT"); pa.nt = e ? atoi(e) : 1; }
+    const int uvar = getenv("NRX_PLACE_U") ? atoi(getenv("NRX_PLACE_U")) : 4;       // fetches in flight per lane (4 | 8)
+    // full-line form (embed_bwd_place_lines_kernel): 64-byte rows whose feature pairs (2j, 2j + 1) are one aligned 128-byte line of the
+    // upstream rows (and of the forward concat); NRX_PLACE_LINES=0 keeps the one-feature-per-lane-group form
+    bool lines = ql == 2 && !unal && pa.nt != 0 && pa.stnt == 0 && (g_out != nullptr || has_fm) && (reinterpret_cast<uintptr_t>(g_out) & 127) == 0 &&
+                 (g_out == nullptr || (out_ld & 31) == 0) && n_place <= 64;
+    if (lines && has_fm) lines = (reinterpret_cast<uintptr_t>(pa.feat) & 127) == 0 && (pa.feat_ld & 31) == 0;
+    pa.fm_mask = 0;
+    for (int i = 0; i < n_place; ++i) {
+        if (pa.fm[i]) pa.fm_mask |= 1ull << i;
+        if (pa.wide_col[i] >= 0) lines = false;
+        if ((i & 1) == 0 ? (pa.out_col[i] & 31) != 0 : pa.out_col[i] != pa.out_col[i - 1] + 16) lines = false;
+    }
+    { const char* e = getenv("NRX_PLACE_LINES"); if (e && atoi(e) == 0) lines = false; }
+    pa.multi_shift = 0;
+    if (c.multi_bases != nullptr) {      // several destination buffers: the one-feature-per-lane-group form carries the base table (in grad[])
+        for (int i = 0; i < c.multi_n; ++i) pa.grad[i] = c.multi_bases[i];
+        pa.multi_shift = c.multi_shift;
+        const unsigned pgrid = (unsigned)((batch + tb - 1) / tb);
+        const size_t plds = (size_t)n_place * tb * 4;
+        if (ql == 2) { if (has_fm) hipLaunchKernelGGL((embed_bwd_place_kernel<2, 4, true, false, false, true>), dim3(pgrid), dim3(NRX_BLOCK), plds, st, pa);
+                       else hipLaunchKernelGGL((embed_bwd_place_kernel<2, 4, false, false, false, true>), dim3(pgrid), dim3(NRX_BLOCK), plds, st, pa); }
+        else if (ql == 3) { if (has_fm) hipLaunchKernelGGL((embed_bwd_place_kernel<3, 4, true, false, false, true>), dim3(pgrid), dim3(NRX_BLOCK), plds, st, pa);
+                            else hipLaunchKernelGGL((embed_bwd_place_kernel<3, 4, false, false, false, true>), dim3(pgrid), dim3(NRX_BLOCK), plds, st, pa); }
+        else { if (has_fm) hipLaunchKernelGGL((embed_bwd_place_kernel<4, 4, true, false, false, true>), dim3(pgrid), dim3(NRX_BLOCK), plds, st, pa);
+               else hipLaunchKernelGGL((embed_bwd_place_kernel<4, 4, false, false, false, true>), dim3(pgrid), dim3(NRX_BLOCK), plds, st, pa); }
+        return;
+    }
+    if (lines) {
+        const unsigned lgrid = (unsigned)((batch + 31) / 32);
+        const size_t llds = (size_t)n_place * PLACE_LINES_TBP * 4;
+        if (g_out == nullptr && dense) hipLaunchKernelGGL((embed_bwd_place_lines_kernel<NRX_LINES_U, true, true, false>), dim3(lgrid), dim3(NRX_BLOCK), llds, st, pa);
+        else if (g_out == nullptr) hipLaunchKernelGGL((embed_bwd_place_lines_kernel<NRX_LINES_U, true, false, false>), dim3(lgrid), dim3(NRX_BLOCK), llds, st, pa);
+        else if (dense && has_fm) hipLaunchKernelGGL((embed_bwd_place_lines_kernel<NRX_LINES_U, true, true>), dim3(lgrid), dim3(NRX_BLOCK), llds, st, pa);
+        else if (dense) hipLaunchKernelGGL((embed_bwd_place_lines_kernel<NRX_LINES_U, false, true>), dim3(lgrid), dim3(NRX_BLOCK), llds, st, pa);
+        else if (has_fm) hipLaunchKernelGGL((embed_bwd_place_lines_kernel<NRX_LINES_U, true, false>), dim3(lgrid), dim3(NRX_BLOCK), llds, st, pa);
+        else hipLaunchKernelGGL((embed_bwd_place_lines_kernel<NRX_LINES_U, false, false>), dim3(lgrid), dim3(NRX_BLOCK), llds, st, pa);
+    } else {
+        const unsigned pgrid = (unsigned)((batch + tb - 1) / tb);
+        const size_t plds = (size_t)n_place * tb * 4;
+        constexpr int U = 8;
 #ifndef NRX_PLACE_UDEF
 #define NRX_PLACE_UDEF 4                // fetches in flight per lane of the one-feature-per-lane-group form (build-time knob)
 #endif
@@ -3713,157 +3693,211 @@ static int embed_bwd_sorted_impl(const nrx_feature_t* feats, int32_t n_feats, in
         else if (uvar == 4) hipLaunchKernelGGL((embed_bwd_place_kernel<QL_, NRX_PLACE_UDEF, false, false>), dim3(pgrid), dim3(NRX_BLOCK), plds, st, pa);        \
         else hipLaunchKernelGGL((embed_bwd_place_kernel<QL_, U, false, false>), dim3(pgrid), dim3(NRX_BLOCK), plds, st, pa);        \
     }
-            if (ql == 2) NRX_PL(2) else if (ql == 3) NRX_PL(3) else NRX_PL(4)
+        if (ql == 2) NRX_PL(2) else if (ql == 3) NRX_PL(3) else NRX_PL(4)
 #undef NRX_PL
-            }
-        }
-        };
-        // Pair plans with an auxiliary stream: the pair pass, the walk and the work lists are short chains of dependent round trips (18 + 10 + 9 us
-        // on C2, nearly all of it latency); the placement pass is 60 us of streaming.  They touch disjoint rows: the small launches go to the
-        // auxiliary stream FIRST (they get their wavefront slots before the placement pass fills every compute unit), the placement pass follows
-        // on the caller's stream, which then waits for the auxiliary one.
-        const bool side = pairs && aux_stream != nullptr && aux_stream != stream;
-        hipStream_t sw = side ? reinterpret_cast<hipStream_t>(aux_stream) : st;
-        static thread_local hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-        if (side) {
-            if (ev_fork == nullptr) {
-                if (hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ev_join, hipEventDisableTiming) != hipSuccess) {
-                    nrx_set_error("nrx_embed_bwd_placed_pairs: hipEventCreate failed");
-                    return NRX_ERR_LAUNCH;
-                }
-            }
-            if (hipEventRecord(ev_fork, st) != hipSuccess || hipStreamWaitEvent(sw, ev_fork, 0) != hipSuccess) {
-                nrx_set_error("nrx_embed_bwd_placed_pairs: fork onto the auxiliary stream failed");
-                return NRX_ERR_LAUNCH;
-            }
-        }
-        if (!side) launch_place();
-        if (place_only) {
-            NRX_LAUNCH_CHECK("nrx_embed_bwd_scatter");
-            return NRX_OK;
-        }
-        unsigned pair_blocks = 0;
-        if (pairs) {
-            // (a plan with pair rows is a placement plan over single-valued features: the launch is `placed`, has no bags)
-            const int64_t pgroups = (off / 2 + 1 + (NRX_BLOCK >> ql) - 1) / (NRX_BLOCK >> ql);      // (at most every second lookup starts a pair)
-            pair_blocks = (unsigned)(pgroups < 512 ? pgroups : 512);
-            a.scale = reinterpret_cast<const float*>(pair_recs);
-            a.bag_inv = reinterpret_cast<const float*>(n_pairs);
-            a.bag_bits = reinterpret_cast<const uint32_t*>(static_cast<intptr_t>(pair_blocks));
-            if (unal) {        // column routing: the records in a launch of their own (the fused walk form exists for the aligned shapes)
-                if (ql == 2) hipLaunchKernelGGL((embed_bwd_pairs_kernel<2, false, true, 0>), dim3(pair_blocks), dim3(NRX_BLOCK), 0, sw, a);
-                else if (ql == 3) hipLaunchKernelGGL((embed_bwd_pairs_kernel<3, false, true, 0>), dim3(pair_blocks), dim3(NRX_BLOCK), 0, sw, a);
-                else hipLaunchKernelGGL((embed_bwd_pairs_kernel<4, false, true, 0>), dim3(pair_blocks), dim3(NRX_BLOCK), 0, sw, a);
-                pair_blocks = 0;
-            }
-        }
-        if (has_bag) {
-            char* end = reinterpret_cast<char*>(a.long_ws + 4) + a.long_items_cap * sizeof(LongItem) +
-                        a.long_slots_cap * sizeof(LongMulti) + a.long_slots_cap * (size_t)dim * 4;
-            float* scale = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(end) + 15) & ~(uintptr_t)15);
-            float* inv = scale + ((off + 15) & ~(int64_t)15);
-            uint32_t* bits = reinterpret_cast<uint32_t*>(inv + ((off + 15) & ~(int64_t)15));
-            a.scale = scale;
-            a.bag_inv = inv;
-            a.bag_bits = bits;
-            if (!(placed && n_place > 0) && workspace != nullptr) {
-                if (nrx_zero2_async(a.long_ws, 16, bits, (size_t)(off / 32 + 2) * 4, st) != NRX_OK) return NRX_ERR_LAUNCH;
-            } else if (nrx_zero_async(bits, (size_t)(off / 32 + 2) * 4, st) != NRX_OK) return NRX_ERR_LAUNCH;
-            // pre-scaled upstream rows of the 0/1-weight bag features ([batch, dim] each) live behind the bit words -- when the
-            // caller's workspace is known to hold them (nrx_embed_bwd_workspace_for) and the launch reads g_out aligned
-            float* gs = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(bits + off / 32 + 2) + 255) & ~(uintptr_t)255);
-            // (every feature gets a block of the staging array: a single-valued feature's rows are copied, as "bags of one with
-            // weight 1" -- then one array serves every lookup of the launch and a row is named by a 32-bit number: pass_staged)
-            bool all_01 = true;                  // kinds whose factor is per SAMPLE when the weights are 0/1
-            for (int i = 0; i < n_feats; ++i) all_01 &= feats[i].kind != NRX_BAG_SUM;
-            const int64_t gs_end = (reinterpret_cast<char*>(gs) - reinterpret_cast<char*>(workspace)) + (int64_t)n_feats * batch * dim * 4;
-            const char* gs_env = getenv("NRX_BAG_PRESCALE");             // "0": the per-lookup factor form (tests compare the two)
-            const bool use_gs = bag_shape && g_out != nullptr && ws_bytes >= gs_end && !(gs_env && gs_env[0] == '0') &&
-                                (int64_t)n_feats * batch < 0x7fffffffLL;
-            if (use_gs && all_01) a.gs_all = gs;
-            StageArgs sg;
-            int n_sg = 0;
-            for (int i = 0; i < n_feats; ++i) {
-                if (batch == 0) continue;
-                float* gsi = (use_gs && feats[i].kind != NRX_BAG_SUM) ? gs + (int64_t)i * batch * dim : nullptr;
-                if (feats[i].kind == NRX_SPARSE) {
-                    if (a.gs_all != nullptr) {
-                        a.f[i].table = gsi;
-                        sg.out_col[n_sg] = feats[i].out_col;
-                        sg.block[n_sg] = i;
-                        ++n_sg;
-                    }
-                    continue;
-                }
+    }
+}
+
+// Bag features: per-lookup scale, per-sample factor and weight bits behind the work lists (bag_scale_kernel), the pre-scaled rows behind those
+static int sorted_bwd_prepare_bags(const SortedBwdCall& c, const SortedBwdShape& s, SortedBwdArgs& a, bool place_runs, hipStream_t st) {
+    const nrx_feature_t* feats = c.feats;
+    const int32_t n_feats = c.n_feats, dim = c.dim;
+    const int64_t batch = c.batch, out_ld = c.out_ld, off = a.off[n_feats];
+    const float* g_out = c.g_out;
+    char* end = reinterpret_cast<char*>(a.long_ws + 4) + a.long_items_cap * sizeof(LongItem) +
+                a.long_slots_cap * sizeof(LongMulti) + a.long_slots_cap * (size_t)dim * 4;
+    float* scale = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(end) + 15) & ~(uintptr_t)15);
+    float* inv = scale + ((off + 15) & ~(int64_t)15);
+    uint32_t* bits = reinterpret_cast<uint32_t*>(inv + ((off + 15) & ~(int64_t)15));
+    a.scale = scale;
+    a.bag_inv = inv;
+    a.bag_bits = bits;
+    if (!place_runs && c.workspace != nullptr) {
+        if (nrx_zero2_async(a.long_ws, 16, bits, (size_t)(off / 32 + 2) * 4, st) != NRX_OK) return NRX_ERR_LAUNCH;
+    } else if (nrx_zero_async(bits, (size_t)(off / 32 + 2) * 4, st) != NRX_OK) return NRX_ERR_LAUNCH;
+    // pre-scaled upstream rows of the 0/1-weight bag features ([batch, dim] each) live behind the bit words -- when the
+    // caller's workspace is known to hold them (nrx_embed_bwd_workspace_for) and the launch reads g_out aligned
+    float* gs = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(bits + off / 32 + 2) + 255) & ~(uintptr_t)255);
+    // (every feature gets a block of the staging array: a single-valued feature's rows are copied, as "bags of one with
+    // weight 1" -- then one array serves every lookup of the launch and a row is named by a 32-bit number: pass_staged)
+    bool all_01 = true;                  // kinds whose factor is per SAMPLE when the weights are 0/1
+    for (int i = 0; i < n_feats; ++i) all_01 &= feats[i].kind != NRX_BAG_SUM;
+    const int64_t gs_end = (reinterpret_cast<char*>(gs) - reinterpret_cast<char*>(c.workspace)) + (int64_t)n_feats * batch * dim * 4;
+    const char* gs_env = getenv("NRX_BAG_PRESCALE");             // "0": the per-lookup factor form (tests compare the two)
+    const bool use_gs = s.bag_shape && g_out != nullptr && c.ws_bytes >= gs_end && !(gs_env && gs_env[0] == '0') &&
+                        (int64_t)n_feats * batch < 0x7fffffffLL;
+    if (use_gs && all_01) a.gs_all = gs;
+    StageArgs sg;
+    int n_sg = 0;
+    for (int i = 0; i < n_feats; ++i) {
+        if (batch == 0) continue;
+        float* gsi = (use_gs && feats[i].kind != NRX_BAG_SUM) ? gs + (int64_t)i * batch * dim : nullptr;
+        if (feats[i].kind == NRX_SPARSE) {
+            if (a.gs_all != nullptr) {
                 a.f[i].table = gsi;
-                const int64_t groups16 = batch;                                          // 16 lanes per sample
-                hipLaunchKernelGGL(bag_scale_kernel, dim3((unsigned)((groups16 * 16 + NRX_BLOCK - 1) / NRX_BLOCK)), dim3(NRX_BLOCK), 0, st,
-                                   a.f[i].weight, (int)feats[i].kind, batch, (int)feats[i].bag_len, scale + a.off[i], inv + a.off[i], bits,
-                                   a.off[i], a.long_ws + 3, feats[i].index, (int)(feats[i].index_bits == 64), g_out, out_ld,
-                                   (int)feats[i].out_col, (int)dim, gsi);
+                sg.out_col[n_sg] = feats[i].out_col;
+                sg.block[n_sg] = i;
+                ++n_sg;
             }
-            if (n_sg > 0)
-                hipLaunchKernelGGL(stage_rows_kernel, dim3((unsigned)((batch * (dim / 4) + NRX_BLOCK - 1) / NRX_BLOCK), (unsigned)n_sg),
-                                   dim3(NRX_BLOCK), 0, st, sg, g_out, out_ld, batch, (int)(dim / 4), gs);
+            continue;
         }
-        const bool reg = a.regular && (g_out != nullptr || has_fm) && !unal;        // arithmetic decode (embed_bwd_sorted_fast_kernel<.., DEC = 1>)
-        const bool few = n_feats <= 4;                                  // scalar decode (DEC = 2); else the LDS table (DEC = 0)
+        a.f[i].table = gsi;
+        const int64_t groups16 = batch;                                          // 16 lanes per sample
+        hipLaunchKernelGGL(bag_scale_kernel, dim3((unsigned)((groups16 * 16 + NRX_BLOCK - 1) / NRX_BLOCK)), dim3(NRX_BLOCK), 0, st,
+                           a.f[i].weight, (int)feats[i].kind, batch, (int)feats[i].bag_len, scale + a.off[i], inv + a.off[i], bits,
+                           a.off[i], a.long_ws + 3, feats[i].index, (int)(feats[i].index_bits == 64), g_out, out_ld,
+                           (int)feats[i].out_col, (int)dim, gsi);
+    }
+    if (n_sg > 0)
+        hipLaunchKernelGGL(stage_rows_kernel, dim3((unsigned)((batch * (dim / 4) + NRX_BLOCK - 1) / NRX_BLOCK), (unsigned)n_sg),
+                           dim3(NRX_BLOCK), 0, st, sg, g_out, out_ld, batch, (int)(dim / 4), gs);
+    return NRX_OK;
+}
+
+// The walk over the sorted rows (plus the blocks of the pair records), then the work lists of the long rows.
+static void sorted_bwd_launch_walk(const SortedBwdCall& c, const SortedBwdShape& s, const SortedBwdArgs& a, int64_t n_rows, unsigned pair_blocks, hipStream_t st) {
+    constexpr int R = 4;
+    constexpr int RB = 2;                   // bag launches: 2 rows x 4 entries per pass (see the kernel)
+    const int ql = s.ql, tb = NRX_BLOCK >> ql;
+    const bool has_fm = s.has_fm, unal = s.unal, has_bag = s.has_bag, placed = s.placed, reg = s.reg, few = s.few;
+    const bool wide_pass = s.bag_shape || placed;       // placement mode: every walked row has >= 2 entries -> 2 rows x 4 entries too
+    const int64_t groups = (n_rows + (wide_pass ? RB : R) - 1) / (wide_pass ? RB : R);
+    unsigned grid = (unsigned)((groups + tb - 1) / tb);
+    {   // the walk's blocks stride over the row groups: when the row count is a device-side number (n_rows is only its bound) a few rounds of resident blocks are enough
+        static const int cap = getenv("NRX_WALK_GRID") ? atoi(getenv("NRX_WALK_GRID")) : 4096;
+        if ((c.n_unique_dev != nullptr || placed) && cap > 0 && grid > (unsigned)cap) grid = (unsigned)cap;
+        if (c.pairs() && grid > 512u) grid = 512u;      // (only the rows looked up 3+ times are walked: a few per thousand lookups on near-unique ids)
+    }
+    // (4 rows x 4 entries per lane group instead of 2 x 4: C5 446.9 -> 458.1 us, C3 163.2 -> 169.6 -- measured, not kept)
 #define NRX_SF(QL_)                                                                                                        \
     {                                                                                                                      \
-        if (pair_blocks != 0 && has_fm && reg) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, true, false, false, 4, 1, true>), dim3(grid + pair_blocks), dim3(NRX_BLOCK), 0, sw, a); \
-        else if (pair_blocks != 0 && has_fm) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, true, false, false, 4, 0, true>), dim3(grid + pair_blocks), dim3(NRX_BLOCK), 0, sw, a); \
-        else if (pair_blocks != 0 && reg) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, false, false, false, 4, 1, true>), dim3(grid + pair_blocks), dim3(NRX_BLOCK), 0, sw, a); \
-        else if (pair_blocks != 0) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, false, false, false, 4, 0, true>), dim3(grid + pair_blocks), dim3(NRX_BLOCK), 0, sw, a); \
-        else if (placed && has_fm && reg) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, true, false, false, 4, 1>), dim3(grid), dim3(NRX_BLOCK), 0, sw, a); \
-        else if (placed && !has_bag && !unal && !has_fm && reg) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, false, false, false, 4, 1>), dim3(grid), dim3(NRX_BLOCK), 0, sw, a); \
-        else if (!placed && has_fm && reg) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, R, true, false, false, 1, 1>), dim3(grid), dim3(NRX_BLOCK), 0, sw, a); \
-        else if (!placed && !has_fm && !unal && !has_bag && reg) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, R, false, false, false, 1, 1>), dim3(grid), dim3(NRX_BLOCK), 0, sw, a); \
-        else if (placed && has_fm) { if (few) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, true, false, false, 4, 2>), dim3(grid), dim3(NRX_BLOCK), 0, sw, a); else hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, true, false, false, 4, 0>), dim3(grid), dim3(NRX_BLOCK), 0, sw, a); } \
-        else if (placed && unal) { if (few) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, false, true, true, 4, 2>), dim3(grid), dim3(NRX_BLOCK), 0, sw, a); else hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, false, true, true, 4, 0>), dim3(grid), dim3(NRX_BLOCK), 0, sw, a); } \
-        else if (placed && !has_bag) { if (few) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, false, false, false, 4, 2>), dim3(grid), dim3(NRX_BLOCK), 0, sw, a); else hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, false, false, false, 4, 0>), dim3(grid), dim3(NRX_BLOCK), 0, sw, a); } \
-        else if (has_fm) { if (few) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, R, true, false, false, 1, 2>), dim3(grid), dim3(NRX_BLOCK), 0, sw, a); else hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, R, true, false, false, 1, 0>), dim3(grid), dim3(NRX_BLOCK), 0, sw, a); } \
-        else if (unal) { if (few) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, R, false, true, true, 1, 2>), dim3(grid), dim3(NRX_BLOCK), 0, sw, a); else hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, R, false, true, true, 1, 0>), dim3(grid), dim3(NRX_BLOCK), 0, sw, a); } \
-        else if (has_bag) { if (few) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, false, true, false, 4, 2>), dim3(grid), dim3(NRX_BLOCK), 0, sw, a); else hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, false, true, false, 4, 0>), dim3(grid), dim3(NRX_BLOCK), 0, sw, a); } \
-        else { if (few) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, R, false, false, false, 1, 2>), dim3(grid), dim3(NRX_BLOCK), 0, sw, a); else hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, R, false, false, false, 1, 0>), dim3(grid), dim3(NRX_BLOCK), 0, sw, a); } \
+        if (pair_blocks != 0 && has_fm && reg) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, true, false, false, 4, 1, true>), dim3(grid + pair_blocks), dim3(NRX_BLOCK), 0, st, a); \
+        else if (pair_blocks != 0 && has_fm) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, true, false, false, 4, 0, true>), dim3(grid + pair_blocks), dim3(NRX_BLOCK), 0, st, a); \
+        else if (pair_blocks != 0 && reg) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, false, false, false, 4, 1, true>), dim3(grid + pair_blocks), dim3(NRX_BLOCK), 0, st, a); \
+        else if (pair_blocks != 0) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, false, false, false, 4, 0, true>), dim3(grid + pair_blocks), dim3(NRX_BLOCK), 0, st, a); \
+        else if (placed && has_fm && reg) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, true, false, false, 4, 1>), dim3(grid), dim3(NRX_BLOCK), 0, st, a); \
+        else if (placed && !has_bag && !unal && !has_fm && reg) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, false, false, false, 4, 1>), dim3(grid), dim3(NRX_BLOCK), 0, st, a); \
+        else if (!placed && has_fm && reg) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, R, true, false, false, 1, 1>), dim3(grid), dim3(NRX_BLOCK), 0, st, a); \
+        else if (!placed && !has_fm && !unal && !has_bag && reg) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, R, false, false, false, 1, 1>), dim3(grid), dim3(NRX_BLOCK), 0, st, a); \
+        else if (placed && has_fm) { if (few) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, true, false, false, 4, 2>), dim3(grid), dim3(NRX_BLOCK), 0, st, a); else hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, true, false, false, 4, 0>), dim3(grid), dim3(NRX_BLOCK), 0, st, a); } \
+        else if (placed && unal) { if (few) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, false, true, true, 4, 2>), dim3(grid), dim3(NRX_BLOCK), 0, st, a); else hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, false, true, true, 4, 0>), dim3(grid), dim3(NRX_BLOCK), 0, st, a); } \
+        else if (placed && !has_bag) { if (few) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, false, false, false, 4, 2>), dim3(grid), dim3(NRX_BLOCK), 0, st, a); else hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, false, false, false, 4, 0>), dim3(grid), dim3(NRX_BLOCK), 0, st, a); } \
+        else if (has_fm) { if (few) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, R, true, false, false, 1, 2>), dim3(grid), dim3(NRX_BLOCK), 0, st, a); else hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, R, true, false, false, 1, 0>), dim3(grid), dim3(NRX_BLOCK), 0, st, a); } \
+        else if (unal) { if (few) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, R, false, true, true, 1, 2>), dim3(grid), dim3(NRX_BLOCK), 0, st, a); else hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, R, false, true, true, 1, 0>), dim3(grid), dim3(NRX_BLOCK), 0, st, a); } \
+        else if (has_bag) { if (few) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, false, true, false, 4, 2>), dim3(grid), dim3(NRX_BLOCK), 0, st, a); else hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, RB, false, true, false, 4, 0>), dim3(grid), dim3(NRX_BLOCK), 0, st, a); } \
+        else { if (few) hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, R, false, false, false, 1, 2>), dim3(grid), dim3(NRX_BLOCK), 0, st, a); else hipLaunchKernelGGL((embed_bwd_sorted_fast_kernel<QL_, R, false, false, false, 1, 0>), dim3(grid), dim3(NRX_BLOCK), 0, st, a); } \
     }
-        if (ql == 2) NRX_SF(2) else if (ql == 3) NRX_SF(3) else NRX_SF(4)
+    if (ql == 2) NRX_SF(2) else if (ql == 3) NRX_SF(3) else NRX_SF(4)
 #undef NRX_SF
-        if (workspace != nullptr) {
-            // (grid: 2048 blocks = 8192 wavefronts striding over the items; 1024 / 4096 measured, no difference on Zipf or uniform ids)
-            const unsigned long_grid = 2048u;
+    if (c.workspace != nullptr) {
+        // (grid: 2048 blocks = 8192 wavefronts striding over the items; 1024 / 4096 measured, no difference on Zipf or uniform ids)
+        const unsigned long_grid = 2048u;
 #define NRX_SL(QL_)                                                                                                        \
     {                                                                                                                      \
-        if (has_fm && reg) hipLaunchKernelGGL((sorted_long_kernel<QL_, true, false, false, 1>), dim3(long_grid), dim3(NRX_BLOCK), 0, sw, a);      \
-        else if (!has_fm && !unal && !has_bag && reg) hipLaunchKernelGGL((sorted_long_kernel<QL_, false, false, false, 1>), dim3(long_grid), dim3(NRX_BLOCK), 0, sw, a); \
-        else if (has_fm) { if (few) hipLaunchKernelGGL((sorted_long_kernel<QL_, true, false, false, 2>), dim3(long_grid), dim3(NRX_BLOCK), 0, sw, a); else hipLaunchKernelGGL((sorted_long_kernel<QL_, true, false, false, 0>), dim3(long_grid), dim3(NRX_BLOCK), 0, sw, a); } \
-        else if (unal) { if (few) hipLaunchKernelGGL((sorted_long_kernel<QL_, false, true, true, 2>), dim3(long_grid), dim3(NRX_BLOCK), 0, sw, a); else hipLaunchKernelGGL((sorted_long_kernel<QL_, false, true, true, 0>), dim3(long_grid), dim3(NRX_BLOCK), 0, sw, a); } \
-        else if (has_bag) { if (few) hipLaunchKernelGGL((sorted_long_kernel<QL_, false, true, false, 2>), dim3(long_grid), dim3(NRX_BLOCK), 0, sw, a); else hipLaunchKernelGGL((sorted_long_kernel<QL_, false, true, false, 0>), dim3(long_grid), dim3(NRX_BLOCK), 0, sw, a); } \
-        else { if (few) hipLaunchKernelGGL((sorted_long_kernel<QL_, false, false, false, 2>), dim3(long_grid), dim3(NRX_BLOCK), 0, sw, a); else hipLaunchKernelGGL((sorted_long_kernel<QL_, false, false, false, 0>), dim3(long_grid), dim3(NRX_BLOCK), 0, sw, a); } \
+        if (has_fm && reg) hipLaunchKernelGGL((sorted_long_kernel<QL_, true, false, false, 1>), dim3(long_grid), dim3(NRX_BLOCK), 0, st, a);      \
+        else if (!has_fm && !unal && !has_bag && reg) hipLaunchKernelGGL((sorted_long_kernel<QL_, false, false, false, 1>), dim3(long_grid), dim3(NRX_BLOCK), 0, st, a); \
+        else if (has_fm) { if (few) hipLaunchKernelGGL((sorted_long_kernel<QL_, true, false, false, 2>), dim3(long_grid), dim3(NRX_BLOCK), 0, st, a); else hipLaunchKernelGGL((sorted_long_kernel<QL_, true, false, false, 0>), dim3(long_grid), dim3(NRX_BLOCK), 0, st, a); } \
+        else if (unal) { if (few) hipLaunchKernelGGL((sorted_long_kernel<QL_, false, true, true, 2>), dim3(long_grid), dim3(NRX_BLOCK), 0, st, a); else hipLaunchKernelGGL((sorted_long_kernel<QL_, false, true, true, 0>), dim3(long_grid), dim3(NRX_BLOCK), 0, st, a); } \
+        else if (has_bag) { if (few) hipLaunchKernelGGL((sorted_long_kernel<QL_, false, true, false, 2>), dim3(long_grid), dim3(NRX_BLOCK), 0, st, a); else hipLaunchKernelGGL((sorted_long_kernel<QL_, false, true, false, 0>), dim3(long_grid), dim3(NRX_BLOCK), 0, st, a); } \
+        else { if (few) hipLaunchKernelGGL((sorted_long_kernel<QL_, false, false, false, 2>), dim3(long_grid), dim3(NRX_BLOCK), 0, st, a); else hipLaunchKernelGGL((sorted_long_kernel<QL_, false, false, false, 0>), dim3(long_grid), dim3(NRX_BLOCK), 0, st, a); } \
     }
-            if (ql == 2) NRX_SL(2) else if (ql == 3) NRX_SL(3) else NRX_SL(4)
+        if (ql == 2) NRX_SL(2) else if (ql == 3) NRX_SL(3) else NRX_SL(4)
 #undef NRX_SL
 #ifdef NRX_COMBINE_SEPARATE
-            if (ql == 2) hipLaunchKernelGGL((sorted_combine_kernel<2>), dim3(64), dim3(NRX_BLOCK), 0, sw, a);
-            else if (ql == 3) hipLaunchKernelGGL((sorted_combine_kernel<3>), dim3(64), dim3(NRX_BLOCK), 0, sw, a);
-            else hipLaunchKernelGGL((sorted_combine_kernel<4>), dim3(64), dim3(NRX_BLOCK), 0, sw, a);
+        if (ql == 2) hipLaunchKernelGGL((sorted_combine_kernel<2>), dim3(64), dim3(NRX_BLOCK), 0, st, a);
+        else if (ql == 3) hipLaunchKernelGGL((sorted_combine_kernel<3>), dim3(64), dim3(NRX_BLOCK), 0, st, a);
+        else hipLaunchKernelGGL((sorted_combine_kernel<4>), dim3(64), dim3(NRX_BLOCK), 0, st, a);
 #endif
+    }
+}
+
+static int sorted_bwd_run_fast(const SortedBwdCall& c, const SortedBwdShape& s, SortedBwdArgs& a) {
+    const nrx_feature_t* feats = c.feats;
+    const int32_t n_feats = c.n_feats;
+    const int64_t batch = c.batch, off = a.off[n_feats];
+    const int ql = s.ql;
+    const bool dense = c.dense();
+    hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+    int64_t n_rows = c.n_unique;                        // rows of the walk launch (upper bound when the count lives on the device)
+    int n_place = 0;
+    PlaceArgs pa;
+    if (s.placed) {         // the placement pass's features, and what that leaves to the walk
+        int64_t placeable = 0;
+        for (int i = 0; i < n_feats; ++i) {
+            if (!((c.place_feats >> i) & 1ull)) continue;
+            NRX_REQUIRE(feats[i].kind == NRX_SPARSE, "nrx_embed_bwd_placed: feature %d is not single-valued: it cannot be placed", i);
+            pa.off[n_place] = a.off[i];
+            pa.ids[n_place] = feats[i].index;
+            pa.grad[n_place] = const_cast<float*>(feats[i].table);
+            NRX_REQUIRE(!dense || (feats[i].index != nullptr && (feats[i].index_bits == 32 || feats[i].index_bits == 64) &&
+                                   feats[i].index_bits == feats[0].index_bits),
+                        "nrx_embed_bwd_placed_dense: feature %d: the placement pass reads the ids (one width per launch)", i);
+            pa.out_col[n_place] = feats[i].out_col;
+            pa.wide_col[n_place] = feats[i].wide_col;
+            pa.fm[n_place] = a.f[i].fm;
+            placeable += batch;
+            ++n_place;
         }
-        if (side) {
-            if (hipEventRecord(ev_join, sw) != hipSuccess) {
-                nrx_set_error("nrx_embed_bwd_placed_pairs: join of the auxiliary stream failed");
-                return NRX_ERR_LAUNCH;
-            }
-            launch_place();
-            if (hipStreamWaitEvent(st, ev_join, 0) != hipSuccess) {
-                nrx_set_error("nrx_embed_bwd_placed_pairs: join of the auxiliary stream failed");
-                return NRX_ERR_LAUNCH;
-            }
-        }
-        NRX_LAUNCH_CHECK("nrx_embed_bwd_sorted(fast)");
+        // walked rows: >= 2 lookups each, or one lookup of a feature outside the mask, or a table's padding row
+        const int64_t bound = placeable / 2 + (off - placeable) + n_feats + 1;
+        if (bound < n_rows) n_rows = bound;
+        a.walk = c.walk; a.n_walk_dev = c.n_walk; a.n_unique = n_rows;
+    }
+    const bool place_runs = s.placed && n_place > 0 && c.mode != SORTED_BWD_SKIP_PLACE;
+    if (c.workspace != nullptr) {        // long segments (hot rows) go through the wavefront-per-item path
+        a.long_ws = reinterpret_cast<int32_t*>((reinterpret_cast<uintptr_t>(c.workspace) + 15) & ~(uintptr_t)15);
+        a.long_items_cap = off / SORTED_LONG_T + 8;
+        a.long_slots_cap = sorted_long_slots_cap(off);
+        // the four work-list counters are cleared by a kernel (nrx_zero_async), not hipMemsetAsync: inside a captured HIP graph
+        // the 16-byte memset node did not take effect on replay (counters kept growing, the list was read past what was written)
+        // (placement mode: the placement pass clears them -- one launch less)
+        // (launches with bag features: cleared together with the weight-bit words below -- one launch, not two)
+        if (!place_runs && !s.has_bag && nrx_zero_async(a.long_ws, 16, st) != NRX_OK) return NRX_ERR_LAUNCH;
+    }
+    if (place_runs) sorted_bwd_launch_place(c, s, a, pa, n_place, st);
+    if (c.mode == SORTED_BWD_PLACE_ONLY) {
+        NRX_LAUNCH_CHECK("nrx_embed_bwd_scatter");
         return NRX_OK;
     }
-    const unsigned grid = (unsigned)((n_unique + tb - 1) / tb);
-    NRX_QSWITCH(ql, { hipLaunchKernelGGL((embed_bwd_sorted_kernel<QL>), dim3(grid), dim3(NRX_BLOCK), 0, st, a); });
+    unsigned pair_blocks = 0;       // the blocks the walk launch adds for the pair records
+    if (c.pairs()) {
+        // (a plan with pair rows is a placement plan over single-valued features: the launch is `placed`, has no bags)
+        const int64_t pgroups = (off / 2 + 1 + (NRX_BLOCK >> ql) - 1) / (NRX_BLOCK >> ql);      // (at most every second lookup starts a pair)
+        pair_blocks = (unsigned)(pgroups < 512 ? pgroups : 512);
+        a.scale = reinterpret_cast<const float*>(c.pair_recs);
+        a.bag_inv = reinterpret_cast<const float*>(c.n_pairs);
+        a.bag_bits = reinterpret_cast<const uint32_t*>(static_cast<intptr_t>(pair_blocks));
+        if (s.unal) {        // column routing: the records in a launch of their own (the fused walk form exists for the aligned shapes)
+            if (ql == 2) hipLaunchKernelGGL((embed_bwd_pairs_kernel<2, false, true, 0>), dim3(pair_blocks), dim3(NRX_BLOCK), 0, st, a);
+            else if (ql == 3) hipLaunchKernelGGL((embed_bwd_pairs_kernel<3, false, true, 0>), dim3(pair_blocks), dim3(NRX_BLOCK), 0, st, a);
+            else hipLaunchKernelGGL((embed_bwd_pairs_kernel<4, false, true, 0>), dim3(pair_blocks), dim3(NRX_BLOCK), 0, st, a);
+            pair_blocks = 0;
+        }
+    }
+    if (s.has_bag && sorted_bwd_prepare_bags(c, s, a, place_runs, st) != NRX_OK) return NRX_ERR_LAUNCH;
+    sorted_bwd_launch_walk(c, s, a, n_rows, pair_blocks, st);
+    NRX_LAUNCH_CHECK("nrx_embed_bwd_sorted(fast)");
+    return NRX_OK;
+}
+
+static int embed_bwd_sorted_impl(const SortedBwdCall& c) {
+    NRX_REQUIRE(c.feats != nullptr && c.n_feats >= 1 && c.n_feats <= NRX_MAX_FEATURES,
+                "nrx_embed_bwd_sorted: n_feats must be in [1, %d]", NRX_MAX_FEATURES);
+    NRX_REQUIRE(c.batch >= 0 && c.dim >= 1 && c.n_unique >= 0, "nrx_embed_bwd_sorted: bad argument");
+    NRX_REQUIRE(c.g_out != nullptr || c.g_wide != nullptr || (c.fm != nullptr && c.fm->g_fm != nullptr), "nrx_embed_bwd_sorted: no upstream gradient");
+    if (c.n_unique == 0 || c.batch == 0) return NRX_OK;
+    SortedBwdArgs a;
+    bool grads_al;
+    int rc = sorted_bwd_pack(c, a, grads_al);
+    if (rc != NRX_OK) return rc;
+    const SortedBwdShape s = sorted_bwd_classify(c, a, grads_al);
+    a.long_t = s.long_t;
+    rc = sorted_bwd_check_mode(c, s);
+    if (rc != NRX_OK) return rc;
+    if (s.fast) return sorted_bwd_run_fast(c, s, a);
+    const int tb = NRX_BLOCK >> s.ql;
+    const unsigned grid = (unsigned)((c.n_unique + tb - 1) / tb);
+    NRX_QSWITCH(s.ql, { hipLaunchKernelGGL((embed_bwd_sorted_kernel<QL>), dim3(grid), dim3(NRX_BLOCK), 0, reinterpret_cast<hipStream_t>(c.stream), a); });
     NRX_LAUNCH_CHECK("nrx_embed_bwd_sorted");
     return NRX_OK;
 }
@@ -3874,8 +3908,11 @@ extern "C" int nrx_embed_bwd_sorted(const nrx_feature_t* feats, int32_t n_feats,
                                     int64_t n_unique, const int64_t* n_unique_dev, const nrx_fm_grad_t* fm, float* values,
                                     void* workspace, void* stream) {
     NRX_TRACE();
-    return embed_bwd_sorted_impl(feats, n_feats, batch, dim, g_out, out_ld, g_wide, wide_ld, order, seg_start, uniq_keys, n_unique,
-                                 n_unique_dev, fm, values, 0, nullptr, nullptr, nullptr, workspace, 0, stream);
+    SortedBwdCall c;
+    c.feats = feats; c.n_feats = n_feats; c.batch = batch; c.dim = dim; c.g_out = g_out; c.out_ld = out_ld; c.g_wide = g_wide; c.wide_ld = wide_ld;
+    c.order = order; c.seg_start = seg_start; c.uniq_keys = uniq_keys; c.n_unique = n_unique; c.n_unique_dev = n_unique_dev; c.fm = fm;
+    c.values = values; c.workspace = workspace; c.stream = stream;
+    return embed_bwd_sorted_impl(c);
 }
 
 extern "C" int nrx_embed_bwd_placed_dense(const nrx_feature_t* feats, int32_t n_feats, int64_t batch, int32_t dim,
@@ -3889,9 +3926,12 @@ extern "C" int nrx_embed_bwd_placed_dense(const nrx_feature_t* feats, int32_t n_
     NRX_REQUIRE(grad_tables != nullptr, "nrx_embed_bwd_placed_dense: null grad_tables");
     NRX_REQUIRE((dest != nullptr) == (walk != nullptr) && (dest != nullptr) == (n_walk != nullptr),
                 "nrx_embed_bwd_placed_dense: dest, walk and n_walk come together (all null: no placement)");
-    return embed_bwd_sorted_impl(feats, n_feats, batch, dim, g_out, out_ld, g_wide, wide_ld, order, seg_start, uniq_keys, n_unique,
-                                 n_unique_dev, fm, nullptr, place_feats, dest, walk, n_walk, workspace, workspace_bytes, stream,
-                                 grad_tables, n_tables, accumulate);
+    SortedBwdCall c;
+    c.feats = feats; c.n_feats = n_feats; c.batch = batch; c.dim = dim; c.g_out = g_out; c.out_ld = out_ld; c.g_wide = g_wide; c.wide_ld = wide_ld;
+    c.order = order; c.seg_start = seg_start; c.uniq_keys = uniq_keys; c.n_unique = n_unique; c.n_unique_dev = n_unique_dev; c.fm = fm;
+    c.grad_tables = grad_tables; c.n_tables = n_tables; c.add_to = accumulate; c.place_feats = place_feats; c.dest = dest; c.walk = walk; c.n_walk = n_walk;
+    c.workspace = workspace; c.ws_bytes = workspace_bytes; c.stream = stream;
+    return embed_bwd_sorted_impl(c);
 }
 
 // ---- the whole deterministic dense-gradient backward of one launch group in ONE call: plan (nrx_sparse_plan_place) + reduction into the dense
@@ -3900,39 +3940,66 @@ extern "C" int nrx_embed_bwd_placed_dense(const nrx_feature_t* feats, int32_t n_
 // that host work was most of the step.
 static inline size_t nrx_al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-extern "C" int64_t nrx_embed_bwd_dense_sorted_workspace(const nrx_feature_t* feats, int32_t n_feats, int64_t batch, int32_t dim, int32_t n_tables) {
+// The workspace of a one-call entry as byte offsets from its 256-byte-aligned start: the size functions return `bytes`, the entries carve by the offsets.
+// keys: the unique keys and per-table counts live here (dense destination), not in the caller's arrays; pair_recs: the plan may be nrx_sparse_plan_lds's.
+// (`bytes` is what the size functions have always returned -- callers cache it: room for BOTH planners, 512 bytes of slack per size function in the figure.)
+struct PlannedLayout {
+    size_t order, uniq, seg, counts, dest, walk, n_walk, pairs, plan_ws, bwd_ws, bytes;
+    PlannedLayout(int64_t n, int32_t n_tables, bool pair_recs, bool keys, int64_t bwd_bytes) {
+        const size_t nn = (size_t)(n > 0 ? n : 1);
+        size_t w = 0;
+        order = w;      w += nrx_al256(nn * 8);
+        uniq = w;       w += keys ? nrx_al256(nn * 8) : 0;
+        seg = w;        w += nrx_al256((nn + 1) * 8);
+        counts = w;     w += keys ? nrx_al256((size_t)(n_tables + 2) * 8) : 0;
+        dest = w;       w += nrx_al256(nn * 4);
+        walk = w;       w += nrx_al256(nn * 4);
+        n_walk = w;     w += 256;                     // [0] walk rows  [1] pair records
+        pairs = w;      w += pair_recs ? nrx_al256((size_t)(n / 2 + 1) * 16) : 0;
+        plan_ws = w;    w += nrx_al256((size_t)nrx_sparse_plan_workspace(n)) + (pair_recs ? nrx_al256((size_t)nrx_sparse_plan_lds_workspace(n)) : 0);
+        bwd_ws = w;     w += nrx_al256((size_t)bwd_bytes);
+        bytes = w + (pair_recs ? 1024 : 512);
+    }
+};
+
+static int64_t planned_workspace_bytes(const nrx_feature_t* feats, int32_t n_feats, int64_t batch, int32_t dim, int32_t n_tables, bool pair_recs) {
     if (feats == nullptr || n_feats < 1 || n_feats > NRX_MAX_FEATURES || batch < 0 || dim < 1 || n_tables < 1) return -1;
     int64_t n = 0;
     for (int i = 0; i < n_feats; ++i) n += batch * (feats[i].kind == NRX_SPARSE ? 1 : feats[i].bag_len);
     const int64_t pw = nrx_sparse_plan_workspace(n), bw = nrx_embed_bwd_workspace_for(feats, n_feats, batch, dim);
     if (pw < 0 || bw < 0) return -1;
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    return (int64_t)(nrx_al256(nn * 8) * 2 + nrx_al256((nn + 1) * 8) + nrx_al256((size_t)(n_tables + 2) * 8) + nrx_al256(nn * 4) * 2 + 256 +
-                     nrx_al256((size_t)pw) + nrx_al256((size_t)bw) + 512);
+    return (int64_t)PlannedLayout(n, n_tables, pair_recs, true, bw).bytes;
 }
 
-extern "C" int nrx_embed_bwd_dense_sorted(const nrx_feature_t* feats, const int32_t* table_of, int32_t n_feats, int32_t n_tables, int64_t batch,
-                                          int32_t dim, const float* g_out, int64_t out_ld, const float* g_wide, int64_t wide_ld,
-                                          const nrx_fm_grad_t* fm, float* const* grad_tables, int32_t accumulate, int32_t place,
-                                          void* workspace, int64_t workspace_bytes, void* stream) {
-    NRX_TRACE();
-    NRX_REQUIRE(feats && table_of && grad_tables && n_feats >= 1 && n_feats <= NRX_MAX_FEATURES && n_tables >= 1 && n_tables <= NRX_MAX_FEATURES,
-                "nrx_embed_bwd_dense_sorted: bad feature / table count");
-    NRX_REQUIRE(workspace != nullptr && workspace_bytes >= nrx_embed_bwd_dense_sorted_workspace(feats, n_feats, batch, dim, n_tables),
-                "nrx_embed_bwd_dense_sorted: workspace too small (nrx_embed_bwd_dense_sorted_workspace)");
-    if (batch == 0) return NRX_OK;
+// What the three one-call entries share: checks, the plan (either planner), its statistics, the reduction.  The destination (`dense`) is the only
+// thing it branches on: the dense gradient tables (c.grad_tables, c.add_to), keys and counts in the workspace -- or the caller's c.uniq_keys /
+// c.values / counts.  The entry fills c with the upstream operands, the destination and its whole workspace; the plan's fields are set here.
+static int embed_bwd_planned_group(const char* who, SortedBwdCall c, bool dense, const int32_t* table_of, int64_t* counts, bool place,
+                                   bool pair_recs /* the entry takes nrx_sparse_plan_lds's plans */, int32_t planner, void* state, int64_t* stats) {
+    const nrx_feature_t* feats = c.feats;
+    const int32_t n_feats = c.n_feats, n_tables = c.n_tables, dim = c.dim;
+    const int64_t batch = c.batch;
+    void* stream = c.stream;
+    NRX_REQUIRE(feats && table_of && (dense ? c.grad_tables != nullptr : c.uniq_keys && c.values && counts) && n_feats >= 1 && n_feats <= NRX_MAX_FEATURES &&
+                    n_tables >= 1 && n_tables <= NRX_MAX_FEATURES,
+                "%s: %s", who, dense ? "bad feature / table count" : "bad argument");
+    NRX_REQUIRE(c.workspace != nullptr && c.ws_bytes >= planned_workspace_bytes(feats, n_feats, batch, dim, n_tables, pair_recs),
+                "%s: workspace too small (%s_workspace)", who, who);
+    if (batch == 0) {
+        if (dense) return NRX_OK;
+        return nrx_zero_async(counts, sizeof(int64_t) * (size_t)(n_tables + 2), reinterpret_cast<hipStream_t>(stream)) == NRX_OK ? NRX_OK : NRX_ERR_LAUNCH;
+    }
     const void* ids[NRX_MAX_FEATURES];
     int64_t lens[NRX_MAX_FEATURES], rows[NRX_MAX_FEATURES];
-    int64_t n = 0;
+    int64_t n = 0, n_sparse = 0;
     uint64_t pmask = 0;
-    int64_t n_sparse = 0;
     for (int i = 0; i < n_feats; ++i) {
         const nrx_feature_t& s = feats[i];
-        NRX_REQUIRE(s.kind == NRX_SPARSE || (s.kind >= NRX_BAG_MASKED_MEAN && s.kind <= NRX_BAG_SUM), "nrx_embed_bwd_dense_sorted: feature %d: kind %d has no table gradient", i, s.kind);
+        NRX_REQUIRE(s.kind == NRX_SPARSE || (s.kind >= NRX_BAG_MASKED_MEAN && s.kind <= NRX_BAG_SUM), "%s: feature %d: kind %d has no table gradient", who, i, s.kind);
         NRX_REQUIRE(s.index != nullptr && s.index_bits == feats[0].index_bits && (s.index_bits == 32 || s.index_bits == 64),
-                    "nrx_embed_bwd_dense_sorted: feature %d: ids of one width (32 or 64 bits) are needed", i);
-        NRX_REQUIRE(!(s.flags & NRX_FEAT_BAG_CSR), "nrx_embed_bwd_dense_sorted: feature %d: CSR bags are not planned; expand with nrx_csr_to_padded", i);
-        NRX_REQUIRE(table_of[i] >= 0 && table_of[i] < n_tables && s.rows >= 1, "nrx_embed_bwd_dense_sorted: feature %d: bad table / rows", i);
+                    "%s: feature %d: ids of one width (32 or 64 bits) are needed", who, i);
+        NRX_REQUIRE(!(s.flags & NRX_FEAT_BAG_CSR), "%s: feature %d: CSR bags are not planned; expand with nrx_csr_to_padded", who, i);
+        NRX_REQUIRE(table_of[i] >= 0 && table_of[i] < n_tables && s.rows >= 1, "%s: feature %d: bad table / rows", who, i);
         ids[i] = s.index;
         lens[i] = batch * (s.kind == NRX_SPARSE ? 1 : s.bag_len);
         rows[i] = s.rows;
@@ -3940,97 +4007,32 @@ extern "C" int nrx_embed_bwd_dense_sorted(const nrx_feature_t* feats, const int3
         if (s.kind == NRX_SPARSE) { pmask |= 1ull << i; n_sparse += batch; }
     }
     // placement pays when the single-valued features are a fair share of the lookups (ops.place_mask's rule)
-    const bool placed = place != 0 && pmask != 0 && n_sparse * 4 >= n;
-    char* w = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    int64_t* order = (int64_t*)w;     w += nrx_al256(nn * 8);
-    int64_t* uniq = (int64_t*)w;      w += nrx_al256(nn * 8);
-    int64_t* seg = (int64_t*)w;       w += nrx_al256((nn + 1) * 8);
-    int64_t* counts = (int64_t*)w;    w += nrx_al256((size_t)(n_tables + 2) * 8);
-    int32_t* dest = (int32_t*)w;      w += nrx_al256(nn * 4);
-    int32_t* walk = (int32_t*)w;      w += nrx_al256(nn * 4);
-    int64_t* n_walk = (int64_t*)w;    w += 256;
-    void* plan_ws = w;                w += nrx_al256((size_t)nrx_sparse_plan_workspace(n));
-    void* bwd_ws = w;
-    const int64_t bwd_bytes = nrx_embed_bwd_workspace_for(feats, n_feats, batch, dim);
-    int rc;
-    if (placed) rc = nrx_sparse_plan_place(ids, lens, table_of, rows, n_feats, feats[0].index_bits, n_tables, pmask, order, uniq, seg, counts,
-                                           dest, walk, n_walk, plan_ws, stream);
-    else rc = nrx_sparse_plan(ids, lens, table_of, rows, n_feats, feats[0].index_bits, n_tables, order, uniq, seg, counts, plan_ws, stream);
-    if (rc != NRX_OK) return rc;
-    return embed_bwd_sorted_impl(feats, n_feats, batch, dim, g_out, out_ld, g_wide, wide_ld, order, seg, uniq, n, counts, fm, nullptr,
-                                 placed ? pmask : 0, placed ? dest : nullptr, placed ? walk : nullptr, placed ? n_walk : nullptr, bwd_ws,
-                                 bwd_bytes, stream, grad_tables, n_tables, accumulate);
-}
-
-// nrx_embed_bwd_dense_sorted with the planner as an argument: planner == 1 takes the one-kernel planner (nrx_sparse_plan_lds; `state` = its
-// control block) when the launch qualifies, and falls back to the sorted planner when it does not; stats (optional, may be mapped host memory):
-// the plan's duplicate statistics in nrx_sparse_plan_lds's format, from either planner -- what the caller's choice for the NEXT batch needs.
-extern "C" int64_t nrx_embed_bwd_dense_planned_workspace(const nrx_feature_t* feats, int32_t n_feats, int64_t batch, int32_t dim, int32_t n_tables) {
-    const int64_t base = nrx_embed_bwd_dense_sorted_workspace(feats, n_feats, batch, dim, n_tables);
-    if (base < 0) return -1;
-    int64_t n = 0;
-    for (int i = 0; i < n_feats; ++i) n += batch * (feats[i].kind == NRX_SPARSE ? 1 : feats[i].bag_len);
-    return base + (int64_t)nrx_al256((size_t)(n / 2 + 1) * 16) + (int64_t)nrx_al256((size_t)nrx_sparse_plan_lds_workspace(n)) + 512;
-}
-
-extern "C" int nrx_embed_bwd_dense_planned(const nrx_feature_t* feats, const int32_t* table_of, int32_t n_feats, int32_t n_tables, int64_t batch,
-                                           int32_t dim, const float* g_out, int64_t out_ld, const float* g_wide, int64_t wide_ld,
-                                           const nrx_fm_grad_t* fm, float* const* grad_tables, int32_t accumulate, int32_t planner,
-                                           void* state, int64_t* stats, void* workspace, int64_t workspace_bytes, void* stream) {
-    NRX_TRACE();
-    NRX_REQUIRE(feats && table_of && grad_tables && n_feats >= 1 && n_feats <= NRX_MAX_FEATURES && n_tables >= 1 && n_tables <= NRX_MAX_FEATURES,
-                "nrx_embed_bwd_dense_planned: bad feature / table count");
-    NRX_REQUIRE(workspace != nullptr && workspace_bytes >= nrx_embed_bwd_dense_planned_workspace(feats, n_feats, batch, dim, n_tables),
-                "nrx_embed_bwd_dense_planned: workspace too small (nrx_embed_bwd_dense_planned_workspace)");
-    if (batch == 0) return NRX_OK;
-    const void* ids[NRX_MAX_FEATURES];
-    int64_t lens[NRX_MAX_FEATURES], rows[NRX_MAX_FEATURES];
-    int64_t n = 0, n_sparse = 0;
-    uint64_t pmask = 0;
-    for (int i = 0; i < n_feats; ++i) {
-        const nrx_feature_t& s = feats[i];
-        NRX_REQUIRE(s.kind == NRX_SPARSE || (s.kind >= NRX_BAG_MASKED_MEAN && s.kind <= NRX_BAG_SUM), "nrx_embed_bwd_dense_planned: feature %d: kind %d has no table gradient", i, s.kind);
-        NRX_REQUIRE(s.index != nullptr && s.index_bits == feats[0].index_bits && (s.index_bits == 32 || s.index_bits == 64),
-                    "nrx_embed_bwd_dense_planned: feature %d: ids of one width (32 or 64 bits) are needed", i);
-        NRX_REQUIRE(!(s.flags & NRX_FEAT_BAG_CSR), "nrx_embed_bwd_dense_planned: feature %d: CSR bags are not planned; expand with nrx_csr_to_padded", i);
-        NRX_REQUIRE(table_of[i] >= 0 && table_of[i] < n_tables && s.rows >= 1, "nrx_embed_bwd_dense_planned: feature %d: bad table / rows", i);
-        ids[i] = s.index;
-        lens[i] = batch * (s.kind == NRX_SPARSE ? 1 : s.bag_len);
-        rows[i] = s.rows;
-        n += lens[i];
-        if (s.kind == NRX_SPARSE) { pmask |= 1ull << i; n_sparse += batch; }
-    }
-    const bool placed = pmask != 0 && n_sparse * 4 >= n;
-    char* w = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    int64_t* order = (int64_t*)w;     w += nrx_al256(nn * 8);
-    int64_t* uniq = (int64_t*)w;      w += nrx_al256(nn * 8);
-    int64_t* seg = (int64_t*)w;       w += nrx_al256((nn + 1) * 8);
-    int64_t* counts = (int64_t*)w;    w += nrx_al256((size_t)(n_tables + 2) * 8);
-    int32_t* dest = (int32_t*)w;      w += nrx_al256(nn * 4);
-    int32_t* walk = (int32_t*)w;      w += nrx_al256(nn * 4);
-    int64_t* n_walk = (int64_t*)w;    w += 256;                     // [0] walk rows  [1] pair records
-    int32_t* pairs = (int32_t*)w;     w += nrx_al256((size_t)(n / 2 + 1) * 16);
-    void* plan_ws = w;
-    {
-        const size_t a_ = nrx_al256((size_t)nrx_sparse_plan_workspace(n)), b_ = nrx_al256((size_t)nrx_sparse_plan_lds_workspace(n));
-        w += a_ > b_ ? a_ : b_;
-    }
-    void* bwd_ws = w;
-    const int64_t bwd_bytes = nrx_embed_bwd_workspace_for(feats, n_feats, batch, dim);
+    const bool placed = place && pmask != 0 && n_sparse * 4 >= n;
+    c.ws_bytes = nrx_embed_bwd_workspace_for(feats, n_feats, batch, dim);
+    const PlannedLayout L(n, n_tables, pair_recs, dense, c.ws_bytes);
+    char* w = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(c.workspace) + 255) & ~(uintptr_t)255);
+    int64_t *order = (int64_t*)(w + L.order), *seg = (int64_t*)(w + L.seg), *n_walk = (int64_t*)(w + L.n_walk);
+    int64_t* uniq = dense ? (int64_t*)(w + L.uniq) : const_cast<int64_t*>(c.uniq_keys);
+    if (dense) counts = (int64_t*)(w + L.counts);
+    int32_t *dest = (int32_t*)(w + L.dest), *walk = (int32_t*)(w + L.walk), *pairs = (int32_t*)(w + L.pairs);
+    void* plan_ws = w + L.plan_ws;
+    c.workspace = w + L.bwd_ws;
+    c.order = order; c.seg_start = seg; c.uniq_keys = uniq; c.n_unique = n; c.n_unique_dev = counts;
+    c.place_feats = pmask; c.dest = dest; c.walk = walk; c.n_walk = n_walk;
     const int ql = ceil_log2((dim + 3) / 4);
     int rc;
     // the one-kernel planner: every feature single-valued, a width the placement pass takes, the launch inside the planner's shapes
-    if (planner == 1 && state != nullptr && placed && n_sparse == n && dim == (4 << ql) && ql >= 2 && ql <= 4 &&
+    if (pair_recs && planner == 1 && state != nullptr && placed && n_sparse == n && dim == (4 << ql) && ql >= 2 && ql <= 4 &&
         nrx_sparse_plan_lds_ok(lens, table_of, rows, n_feats, n_tables)) {
         rc = nrx_sparse_plan_lds(ids, lens, table_of, rows, n_feats, feats[0].index_bits, n_tables, order, uniq, seg, counts, dest, walk, n_walk,
                                  pairs, n_walk + 1, stats, state, plan_ws, stream);
         if (rc != NRX_OK) return rc;
-        rc = embed_bwd_sorted_impl(feats, n_feats, batch, dim, g_out, out_ld, g_wide, wide_ld, order, seg, uniq, n, counts, fm, nullptr, pmask, dest,
-                                   walk, n_walk, bwd_ws, bwd_bytes, stream, grad_tables, n_tables, accumulate, true, nullptr, pairs, n_walk + 1);
+        c.mode = SORTED_BWD_PAIRS; c.pair_recs = pairs; c.n_pairs = n_walk + 1;
+        rc = embed_bwd_sorted_impl(c);
         if (rc != NRX_ERR_UNSUPPORTED) return rc;           // (outside the pair pass's shapes: nothing was enqueued -- the sorted planner's plan below)
     }
+    c.mode = SORTED_BWD_ALL; c.pair_recs = nullptr; c.n_pairs = nullptr;
+    if (!placed) { c.place_feats = 0; c.dest = nullptr; c.walk = nullptr; c.n_walk = nullptr; }
     if (placed) rc = nrx_sparse_plan_place(ids, lens, table_of, rows, n_feats, feats[0].index_bits, n_tables, pmask, order, uniq, seg, counts,
                                            dest, walk, n_walk, plan_ws, stream);
     else rc = nrx_sparse_plan(ids, lens, table_of, rows, n_feats, feats[0].index_bits, n_tables, order, uniq, seg, counts, plan_ws, stream);
@@ -4039,13 +4041,45 @@ extern "C" int nrx_embed_bwd_dense_planned(const nrx_feature_t* feats, const int
         rc = nrx_sparse_plan_stats(counts, n_walk, n, stats, stream);
         if (rc != NRX_OK) return rc;
     }
-    return embed_bwd_sorted_impl(feats, n_feats, batch, dim, g_out, out_ld, g_wide, wide_ld, order, seg, uniq, n, counts, fm, nullptr,
-                                 placed ? pmask : 0, placed ? dest : nullptr, placed ? walk : nullptr, placed ? n_walk : nullptr, bwd_ws,
-                                 bwd_bytes, stream, grad_tables, n_tables, accumulate);
+    return embed_bwd_sorted_impl(c);
+}
+
+extern "C" int64_t nrx_embed_bwd_dense_sorted_workspace(const nrx_feature_t* feats, int32_t n_feats, int64_t batch, int32_t dim, int32_t n_tables) {
+    return planned_workspace_bytes(feats, n_feats, batch, dim, n_tables, false);
+}
+
+extern "C" int nrx_embed_bwd_dense_sorted(const nrx_feature_t* feats, const int32_t* table_of, int32_t n_feats, int32_t n_tables, int64_t batch,
+                                          int32_t dim, const float* g_out, int64_t out_ld, const float* g_wide, int64_t wide_ld,
+                                          const nrx_fm_grad_t* fm, float* const* grad_tables, int32_t accumulate, int32_t place,
+                                          void* workspace, int64_t workspace_bytes, void* stream) {
+    NRX_TRACE();
+    SortedBwdCall c;
+    c.feats = feats; c.n_feats = n_feats; c.batch = batch; c.dim = dim; c.g_out = g_out; c.out_ld = out_ld; c.g_wide = g_wide; c.wide_ld = wide_ld;
+    c.fm = fm; c.grad_tables = grad_tables; c.n_tables = n_tables; c.add_to = accumulate; c.workspace = workspace; c.ws_bytes = workspace_bytes; c.stream = stream;
+    return embed_bwd_planned_group("nrx_embed_bwd_dense_sorted", c, true, table_of, nullptr, place != 0, false, 0, nullptr, nullptr);
+}
+
+// nrx_embed_bwd_dense_sorted with the planner as an argument: planner == 1 takes the one-kernel planner (nrx_sparse_plan_lds; `state` = its
+// control block) when the launch qualifies, and falls back to the sorted planner when it does not; stats (optional, may be mapped host memory):
+// the plan's duplicate statistics in nrx_sparse_plan_lds's format, from either planner -- what the caller's choice for the NEXT batch needs.
+extern "C" int64_t nrx_embed_bwd_dense_planned_workspace(const nrx_feature_t* feats, int32_t n_feats, int64_t batch, int32_t dim, int32_t n_tables) {
+    return planned_workspace_bytes(feats, n_feats, batch, dim, n_tables, true);
+}
+
+extern "C" int nrx_embed_bwd_dense_planned(const nrx_feature_t* feats, const int32_t* table_of, int32_t n_feats, int32_t n_tables, int64_t batch,
+                                           int32_t dim, const float* g_out, int64_t out_ld, const float* g_wide, int64_t wide_ld,
+                                           const nrx_fm_grad_t* fm, float* const* grad_tables, int32_t accumulate, int32_t planner,
+                                           void* state, int64_t* stats, void* workspace, int64_t workspace_bytes, void* stream) {
+    NRX_TRACE();
+    SortedBwdCall c;
+    c.feats = feats; c.n_feats = n_feats; c.batch = batch; c.dim = dim; c.g_out = g_out; c.out_ld = out_ld; c.g_wide = g_wide; c.wide_ld = wide_ld;
+    c.fm = fm; c.grad_tables = grad_tables; c.n_tables = n_tables; c.add_to = accumulate; c.workspace = workspace; c.ws_bytes = workspace_bytes; c.stream = stream;
+    return embed_bwd_planned_group("nrx_embed_bwd_dense_planned", c, true, table_of, nullptr, true, true, planner, state, stats);
 }
 
 // The row-sparse counterpart of nrx_embed_bwd_dense_planned: plan (either planner) + reduction in ONE call, the unique keys, their summed rows and the
 // per-table counts left in caller-owned arrays (what the fused optimizer's sink holds), every intermediate in one workspace.
+// (the dense figure: the keys and counts it has room for stay unused here)
 extern "C" int64_t nrx_embed_bwd_sparse_planned_workspace(const nrx_feature_t* feats, int32_t n_feats, int64_t batch, int32_t dim, int32_t n_tables) {
     return nrx_embed_bwd_dense_planned_workspace(feats, n_feats, batch, dim, n_tables);
 }
@@ -4055,66 +4089,10 @@ extern "C" int nrx_embed_bwd_sparse_planned(const nrx_feature_t* feats, const in
                                             const nrx_fm_grad_t* fm, int64_t* uniq_keys, float* values, int64_t* counts, int32_t planner,
                                             void* state, int64_t* stats, void* workspace, int64_t workspace_bytes, void* stream) {
     NRX_TRACE();
-    NRX_REQUIRE(feats && table_of && uniq_keys && values && counts && n_feats >= 1 && n_feats <= NRX_MAX_FEATURES && n_tables >= 1 && n_tables <= NRX_MAX_FEATURES,
-                "nrx_embed_bwd_sparse_planned: bad argument");
-    NRX_REQUIRE(workspace != nullptr && workspace_bytes >= nrx_embed_bwd_sparse_planned_workspace(feats, n_feats, batch, dim, n_tables),
-                "nrx_embed_bwd_sparse_planned: workspace too small (nrx_embed_bwd_sparse_planned_workspace)");
-    if (batch == 0) return nrx_zero_async(counts, sizeof(int64_t) * (size_t)(n_tables + 2), reinterpret_cast<hipStream_t>(stream)) == NRX_OK ? NRX_OK : NRX_ERR_LAUNCH;
-    const void* ids[NRX_MAX_FEATURES];
-    int64_t lens[NRX_MAX_FEATURES], rows[NRX_MAX_FEATURES];
-    int64_t n = 0, n_sparse = 0;
-    uint64_t pmask = 0;
-    for (int i = 0; i < n_feats; ++i) {
-        const nrx_feature_t& s = feats[i];
-        NRX_REQUIRE(s.kind == NRX_SPARSE || (s.kind >= NRX_BAG_MASKED_MEAN && s.kind <= NRX_BAG_SUM), "nrx_embed_bwd_sparse_planned: feature %d: kind %d has no table gradient", i, s.kind);
-        NRX_REQUIRE(s.index != nullptr && s.index_bits == feats[0].index_bits && (s.index_bits == 32 || s.index_bits == 64),
-                    "nrx_embed_bwd_sparse_planned: feature %d: ids of one width (32 or 64 bits) are needed", i);
-        NRX_REQUIRE(!(s.flags & NRX_FEAT_BAG_CSR), "nrx_embed_bwd_sparse_planned: feature %d: CSR bags are not planned; expand with nrx_csr_to_padded", i);
-        NRX_REQUIRE(table_of[i] >= 0 && table_of[i] < n_tables && s.rows >= 1, "nrx_embed_bwd_sparse_planned: feature %d: bad table / rows", i);
-        ids[i] = s.index;
-        lens[i] = batch * (s.kind == NRX_SPARSE ? 1 : s.bag_len);
-        rows[i] = s.rows;
-        n += lens[i];
-        if (s.kind == NRX_SPARSE) { pmask |= 1ull << i; n_sparse += batch; }
-    }
-    const bool placed = pmask != 0 && n_sparse * 4 >= n;
-    char* w = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    int64_t* order = (int64_t*)w;     w += nrx_al256(nn * 8);
-    int64_t* seg = (int64_t*)w;       w += nrx_al256((nn + 1) * 8);
-    int32_t* dest = (int32_t*)w;      w += nrx_al256(nn * 4);
-    int32_t* walk = (int32_t*)w;      w += nrx_al256(nn * 4);
-    int64_t* n_walk = (int64_t*)w;    w += 256;                     // [0] walk rows  [1] pair records
-    int32_t* pairs = (int32_t*)w;     w += nrx_al256((size_t)(n / 2 + 1) * 16);
-    void* plan_ws = w;
-    {
-        const size_t a_ = nrx_al256((size_t)nrx_sparse_plan_workspace(n)), b_ = nrx_al256((size_t)nrx_sparse_plan_lds_workspace(n));
-        w += a_ > b_ ? a_ : b_;
-    }
-    void* bwd_ws = w;
-    const int64_t bwd_bytes = nrx_embed_bwd_workspace_for(feats, n_feats, batch, dim);
-    const int ql = ceil_log2((dim + 3) / 4);
-    int rc;
-    if (planner == 1 && state != nullptr && placed && n_sparse == n && dim == (4 << ql) && ql >= 2 && ql <= 4 &&
-        nrx_sparse_plan_lds_ok(lens, table_of, rows, n_feats, n_tables)) {
-        rc = nrx_sparse_plan_lds(ids, lens, table_of, rows, n_feats, feats[0].index_bits, n_tables, order, uniq_keys, seg, counts, dest, walk, n_walk,
-                                 pairs, n_walk + 1, stats, state, plan_ws, stream);
-        if (rc != NRX_OK) return rc;
-        rc = embed_bwd_sorted_impl(feats, n_feats, batch, dim, g_out, out_ld, g_wide, wide_ld, order, seg, uniq_keys, n, counts, fm, values, pmask, dest,
-                                   walk, n_walk, bwd_ws, bwd_bytes, stream, nullptr, 0, 0, true, nullptr, pairs, n_walk + 1);
-        if (rc != NRX_ERR_UNSUPPORTED) return rc;           // (outside the pair pass's shapes: nothing was enqueued -- the sorted planner's plan below)
-    }
-    if (placed) rc = nrx_sparse_plan_place(ids, lens, table_of, rows, n_feats, feats[0].index_bits, n_tables, pmask, order, uniq_keys, seg, counts,
-                                           dest, walk, n_walk, plan_ws, stream);
-    else rc = nrx_sparse_plan(ids, lens, table_of, rows, n_feats, feats[0].index_bits, n_tables, order, uniq_keys, seg, counts, plan_ws, stream);
-    if (rc != NRX_OK) return rc;
-    if (stats != nullptr && placed) {
-        rc = nrx_sparse_plan_stats(counts, n_walk, n, stats, stream);
-        if (rc != NRX_OK) return rc;
-    }
-    return embed_bwd_sorted_impl(feats, n_feats, batch, dim, g_out, out_ld, g_wide, wide_ld, order, seg, uniq_keys, n, counts, fm, values,
-                                 placed ? pmask : 0, placed ? dest : nullptr, placed ? walk : nullptr, placed ? n_walk : nullptr, bwd_ws,
-                                 bwd_bytes, stream);
+    SortedBwdCall c;
+    c.feats = feats; c.n_feats = n_feats; c.batch = batch; c.dim = dim; c.g_out = g_out; c.out_ld = out_ld; c.g_wide = g_wide; c.wide_ld = wide_ld;
+    c.fm = fm; c.uniq_keys = uniq_keys; c.values = values; c.n_tables = n_tables; c.workspace = workspace; c.ws_bytes = workspace_bytes; c.stream = stream;
+    return embed_bwd_planned_group("nrx_embed_bwd_sparse_planned", c, false, table_of, counts, true, true, planner, state, stats);
 }
 
 // workspace size that also holds the pre-scaled upstream rows of the launch's 0/1-weight bag features
@@ -4139,8 +4117,12 @@ extern "C" int nrx_embed_bwd_placed(const nrx_feature_t* feats, int32_t n_feats,
                 "nrx_embed_bwd_placed: dest, walk and n_walk come together (all null: no placement)");
     NRX_REQUIRE(workspace == nullptr || workspace_bytes == 0 || workspace_bytes >= nrx_embed_bwd_sorted_workspace(0, dim),
                 "nrx_embed_bwd_placed: workspace_bytes too small");
-    return embed_bwd_sorted_impl(feats, n_feats, batch, dim, g_out, out_ld, g_wide, wide_ld, order, seg_start, uniq_keys, n_unique,
-                                 n_unique_dev, fm, values, place_feats, dest, walk, n_walk, workspace, workspace_bytes, stream);
+    SortedBwdCall c;
+    c.feats = feats; c.n_feats = n_feats; c.batch = batch; c.dim = dim; c.g_out = g_out; c.out_ld = out_ld; c.g_wide = g_wide; c.wide_ld = wide_ld;
+    c.order = order; c.seg_start = seg_start; c.uniq_keys = uniq_keys; c.n_unique = n_unique; c.n_unique_dev = n_unique_dev; c.fm = fm;
+    c.values = values; c.place_feats = place_feats; c.dest = dest; c.walk = walk; c.n_walk = n_walk;
+    c.workspace = workspace; c.ws_bytes = workspace_bytes; c.stream = stream;
+    return embed_bwd_sorted_impl(c);
 }
 
 // The placement pass alone, with the caller's destinations: values[dest[p]] = the upstream row of lookup p (flat, feature-major), FM term folded
@@ -4154,11 +4136,14 @@ extern "C" int nrx_embed_bwd_scatter(const nrx_feature_t* feats, int32_t n_feats
     for (int i = 0; i < n_feats; ++i)
         NRX_REQUIRE(feats[i].kind == NRX_SPARSE, "nrx_embed_bwd_scatter: feature %d is not single-valued", i);
     const uint64_t mask = n_feats == 64 ? ~0ull : ((1ull << n_feats) - 1ull);
-    // (order / seg_start are the walk's inputs: never read by the placement pass; any non-null address passes the argument checks)
+    SortedBwdCall c; c.mode = SORTED_BWD_PLACE_ONLY;
+    c.feats = feats; c.n_feats = n_feats; c.batch = batch; c.dim = dim; c.g_out = g_out; c.out_ld = out_ld; c.g_wide = g_wide; c.wide_ld = wide_ld;
+    c.fm = fm; c.values = values; c.place_feats = mask; c.dest = dest; c.stream = stream;
+    // order / seg_start / walk / n_walk are the walk's inputs, n_unique its row count: the placement pass reads none of them, but the checks that every
+    // mode shares want them non-null (and n_unique above zero, or the call is empty).  Any address passes: dest stands in, never dereferenced as such.
     const int64_t* dummy = reinterpret_cast<const int64_t*>(dest);
-    return embed_bwd_sorted_impl(feats, n_feats, batch, dim, g_out, out_ld, g_wide, wide_ld, dummy, dummy, nullptr, /*n_unique=*/1, nullptr, fm,
-                                 values, mask, dest, reinterpret_cast<const int32_t*>(dest), dummy, nullptr, 0, stream, nullptr, 0, 0, false, nullptr,
-                                 nullptr, nullptr, /*place_only=*/true);
+    c.order = dummy; c.seg_start = dummy; c.n_unique = 1; c.walk = dest; c.n_walk = dummy;
+    return embed_bwd_sorted_impl(c);
 }
 
 // nrx_embed_bwd_scatter into SEVERAL buffers: dest[p] = (base number << shift) | row -- the owners' gradient arenas as this process maps them.
@@ -4175,10 +4160,13 @@ extern "C" int nrx_embed_bwd_scatter_multi(const nrx_feature_t* feats, int32_t n
     for (int i = 0; i < n_bases; ++i)
         NRX_REQUIRE(bases[i] != nullptr && nrx_aligned16(bases[i]), "nrx_embed_bwd_scatter_multi: base %d: null / unaligned", i);
     const uint64_t mask = n_feats == 64 ? ~0ull : ((1ull << n_feats) - 1ull);
-    const int64_t* dummy = reinterpret_cast<const int64_t*>(dest);
-    return embed_bwd_sorted_impl(feats, n_feats, batch, dim, g_out, out_ld, nullptr, 0, dummy, dummy, nullptr, /*n_unique=*/1, nullptr, fm,
-                                 bases[0], mask, dest, reinterpret_cast<const int32_t*>(dest), dummy, nullptr, 0, stream, nullptr, 0, 0, false, nullptr,
-                                 nullptr, nullptr, /*place_only=*/true, bases, n_bases, shift);
+    SortedBwdCall c; c.mode = SORTED_BWD_PLACE_ONLY;
+    c.feats = feats; c.n_feats = n_feats; c.batch = batch; c.dim = dim; c.g_out = g_out; c.out_ld = out_ld;
+    c.fm = fm; c.values = bases[0]; c.place_feats = mask; c.dest = dest; c.stream = stream;
+    c.multi_bases = bases; c.multi_n = n_bases; c.multi_shift = shift;
+    const int64_t* dummy = reinterpret_cast<const int64_t*>(dest);      // (as in nrx_embed_bwd_scatter: stand-ins for the walk's inputs)
+    c.order = dummy; c.seg_start = dummy; c.n_unique = 1; c.walk = dest; c.n_walk = dummy;
+    return embed_bwd_sorted_impl(c);
 }
 
 // The reduction WITHOUT its placement pass: the rows the plan places (dest >= 0) are in values[] already -- written there by the requesters
@@ -4194,9 +4182,12 @@ extern "C" int nrx_embed_bwd_walk(const nrx_feature_t* feats, int32_t n_feats, i
     NRX_REQUIRE((pairs == nullptr) == (n_pairs == nullptr) && (pairs == nullptr || nrx_aligned16(pairs)), "nrx_embed_bwd_walk: pairs and n_pairs go together");
     for (int i = 0; i < n_feats; ++i)
         NRX_REQUIRE(feats != nullptr && feats[i].kind == NRX_SPARSE, "nrx_embed_bwd_walk: feature %d: single-valued features only", i);
-    return embed_bwd_sorted_impl(feats, n_feats, batch, dim, g_out, out_ld, nullptr, 0, order, seg_start, uniq_keys, n_unique, n_unique_dev, fm, values,
-                                 place_feats, dest, walk, n_walk, workspace, workspace_bytes, stream, nullptr, 0, 0, pairs != nullptr, nullptr, pairs, n_pairs,
-                                 false, nullptr, 0, 0, /*skip_place=*/true);
+    SortedBwdCall c; c.mode = SORTED_BWD_SKIP_PLACE;
+    c.feats = feats; c.n_feats = n_feats; c.batch = batch; c.dim = dim; c.g_out = g_out; c.out_ld = out_ld;
+    c.order = order; c.seg_start = seg_start; c.uniq_keys = uniq_keys; c.n_unique = n_unique; c.n_unique_dev = n_unique_dev; c.fm = fm;
+    c.values = values; c.place_feats = place_feats; c.dest = dest; c.walk = walk; c.n_walk = n_walk; c.pair_recs = pairs; c.n_pairs = n_pairs;
+    c.workspace = workspace; c.ws_bytes = workspace_bytes; c.stream = stream;
+    return embed_bwd_sorted_impl(c);
 }
 
 // nrx_embed_bwd_placed / nrx_embed_bwd_placed_dense for the placement plans of nrx_sparse_plan_lds (pair records for the rows looked up twice).
@@ -4210,6 +4201,7 @@ extern "C" int nrx_embed_bwd_placed_pairs(const nrx_feature_t* feats, int32_t n_
                                           const int32_t* pairs, const int64_t* n_pairs,
                                           void* workspace, int64_t workspace_bytes, void* aux_stream, void* stream) {
     NRX_TRACE();
+    NRX_REQUIRE(aux_stream == nullptr || aux_stream == stream, "nrx_embed_bwd_placed_pairs: aux_stream is reserved: pass NULL (or `stream`)");
     NRX_REQUIRE(dest != nullptr && walk != nullptr && n_walk != nullptr && uniq_keys != nullptr && pairs != nullptr && n_pairs != nullptr,
                 "nrx_embed_bwd_placed_pairs: needs the whole plan (dest, walk, n_walk, pairs, n_pairs, uniq_keys)");
     NRX_REQUIRE(nrx_aligned16(pairs), "nrx_embed_bwd_placed_pairs: pairs must be 16-byte aligned");
@@ -4217,7 +4209,11 @@ extern "C" int nrx_embed_bwd_placed_pairs(const nrx_feature_t* feats, int32_t n_
     NRX_REQUIRE(workspace != nullptr, "nrx_embed_bwd_placed_pairs: needs the work-list workspace (nrx_embed_bwd_workspace_for)");
     for (int i = 0; i < n_feats; ++i)
         NRX_REQUIRE(feats != nullptr && feats[i].kind == NRX_SPARSE && ((place_feats >> i) & 1ull), "nrx_embed_bwd_placed_pairs: feature %d: every feature must be single-valued and placeable", i);
-    return embed_bwd_sorted_impl(feats, n_feats, batch, dim, g_out, out_ld, g_wide, wide_ld, order, seg_start, uniq_keys, n_unique,
-                                 n_unique_dev, fm, values, place_feats, dest, walk, n_walk, workspace, workspace_bytes, stream,
-                                 grad_tables, n_tables, accumulate, true, aux_stream, pairs, n_pairs);
+    SortedBwdCall c; c.mode = SORTED_BWD_PAIRS;
+    c.feats = feats; c.n_feats = n_feats; c.batch = batch; c.dim = dim; c.g_out = g_out; c.out_ld = out_ld; c.g_wide = g_wide; c.wide_ld = wide_ld;
+    c.order = order; c.seg_start = seg_start; c.uniq_keys = uniq_keys; c.n_unique = n_unique; c.n_unique_dev = n_unique_dev; c.fm = fm;
+    c.values = values; c.grad_tables = grad_tables; c.n_tables = n_tables; c.add_to = accumulate; c.pair_recs = pairs; c.n_pairs = n_pairs;
+    c.place_feats = place_feats; c.dest = dest; c.walk = walk; c.n_walk = n_walk;
+    c.workspace = workspace; c.ws_bytes = workspace_bytes; c.stream = stream;
+    return embed_bwd_sorted_impl(c);
 }

@@ -755,23 +755,6 @@ PLAN_LDS = os.environ.get("NRX_PLAN_LDS", "auto")
 _lds_states = {}
 
 
-_aux_streams = {}
-PAIRS_AUX = os.environ.get("NRX_PAIRS_AUX", "0") != "0"      # the pair pass / walk of a one-kernel plan on a second stream, next to the placement
-                                                              # pass: measured, LOSES (C2 213.8 -> 225.1 us: the small launches are chains of dependent
-                                                              # round trips and every trip takes longer under the placement pass's traffic); off
-
-
-def _aux_stream(dev: torch.device) -> Optional[int]:
-    """The stream nrx_embed_bwd_placed_pairs forks its small launches onto (one per device)."""
-    if not PAIRS_AUX:
-        return None
-    k = dev.index if dev.index is not None else torch.cuda.current_device()
-    s = _aux_streams.get(k)
-    if s is None:
-        s = _aux_streams[k] = torch.cuda.Stream(device=dev)
-    return s.cuda_stream
-
-
 def _lds_state(dev: torch.device, stream: int) -> Optional[torch.Tensor]:
     """The planner's persistent control block (ticket, epoch, per-block totals), one per (device, stream): zero before the first use."""
     key = (dev.index if dev.index is not None else torch.cuda.current_device(), int(stream))
@@ -1025,7 +1008,7 @@ def _bwd_sorted(lib, pl, pmask, arr, n, B, D, g_out, ld, g_wide, wide_ld, n_uniq
                                             values.data_ptr() if dense is None else None, dense[0] if dense else None,
                                             dense[1] if dense else 0, dense[2] if dense else 0, int(pmask),
                                             pl[4].data_ptr(), pl[5].data_ptr(), pl[6].data_ptr(), pl[7].data_ptr(), pl[6].data_ptr() + 8,
-                                            lws.data_ptr(), lws.numel(), _aux_stream(pl[0].device), stream)
+                                            lws.data_ptr(), lws.numel(), None, stream)
         if rc == 0:
             return pl
         if rc != NRX_ERR_UNSUPPORTED or replan is None:
@@ -1738,7 +1721,7 @@ class PreparedSparseBackward:
                                                     g["order"].data_ptr(), g["seg"].data_ptr(), g["uniq"].data_ptr(), g["total"],
                                                     g["counts"].data_ptr(), self.fmg, g["values"].data_ptr(), None, 0, 0, g["pmask"],
                                                     g["dest"].data_ptr(), g["walk"].data_ptr(), g["n_walk"].data_ptr(), g["pair_recs"].data_ptr(),
-                                                    g["n_walk"].data_ptr() + 8, g["lws"].data_ptr(), g["lws"].numel(), _aux_stream(f.device), stream)
+                                                    g["n_walk"].data_ptr() + 8, g["lws"].data_ptr(), g["lws"].numel(), None, stream)
                 if rc == NRX_ERR_UNSUPPORTED:           # outside the pair pass's shapes: plan again with the sorted planner and no pair records, for good
                     g["policy"] = None
                     g["sorted_pairs"] = False

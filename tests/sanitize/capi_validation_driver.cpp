@@ -64,6 +64,15 @@ int main() {
         EXPECT_BAD(nrx_gather_rows_segmented(tabs, rows, 2, i64, seg_table, 1, 8, 16, i64, b, nullptr, nullptr));
         if (std::strstr(nrx_last_error(), "table 1") == nullptr) { std::fprintf(stderr, "error text: %s\n", nrx_last_error()); ++failures; }
     }
+    {   // the reserved aux_stream of nrx_embed_bwd_placed_pairs: a stream of its own is refused by the argument checks, before anything is enqueued
+        nrx_feature_t f;
+        std::memset(&f, 0, sizeof f);
+        f.kind = NRX_SPARSE; f.dim = 16; f.rows = 4; f.index = i64; f.index_bits = 64; f.wide_col = -1;
+        const int32_t* i32 = reinterpret_cast<const int32_t*>(i64);
+        EXPECT_BAD(nrx_embed_bwd_placed_pairs(&f, 1, 8, 16, a, 16, nullptr, 0, i64, i64, i64, 8, nullptr, nullptr, b, nullptr, 0, 0, 1, i32, i32, i64,
+                                              i32, i64, a, 4096, /*aux_stream=*/b, /*stream=*/nullptr));
+        if (std::strstr(nrx_last_error(), "aux_stream") == nullptr) { std::fprintf(stderr, "error text: %s\n", nrx_last_error()); ++failures; }
+    }
     std::free(a); std::free(b); std::free(i64);
     if (failures) { std::fprintf(stderr, "%d check(s) failed\n", failures); return 1; }
     std::puts("C-ABI validation sanitize driver: OK");

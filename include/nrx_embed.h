@@ -361,7 +361,39 @@ NRX_API int nrx_sparse_adam_step_bf16_rows(uint16_t* const* tables, float* const
                          float beta2, float eps, float lr_times_weight_decay, uint64_t sr_seed, int64_t step,
                          const int64_t* step_dev, const int64_t* row_mul, const int64_t* row_add, void* stream);
 
-/* Exact dense AdamW from row-sparse gradients ("exact-dense mode").  The reference trains every embedding table with one dense
+/* Fused row-sparse Adagrad over the same unique-row lists as nrx_sparse_adam_step (keys (table << 40) | row, grads[n_unique, dim], optional
+ * n_unique_dev, up to NRX_MAX_FEATURES tables of one `dim`; negative keys, INT64_MAX, tables >= n_tables and row 0 are skipped; every key at most
+ * once).  `flags` selects the mode and the tables' type:
+ *   0 (element-wise)       state[t] is fp32 [rows, dim]; per element
+ *                            s = fma(g, g, s);  w = w - w * lr_times_weight_decay;  w = w - (lr * g) / (sqrtf(s) + eps)
+ *                          -- torch.optim.Adagrad on sparse gradients with lr_decay = 0 and initial_accumulator_value = 0, plus the optional
+ *                          decoupled decay of the touched rows that nrx_sparse_adam_step has.
+ *   NRX_ADAGRAD_ROWWISE    state[t] is fp32 [rows]: ONE accumulator per row,  s = s + S / dim  with S = the row's sum of g_k * g_k; every element
+ *                          of the row then takes the element-wise weight update with that one s.
+ *   NRX_ADAGRAD_TABLE_BF16 tables[t] holds bf16 [rows, dim] (uint16 patterns) instead of fp32; the state is fp32 either way.  The row is widened,
+ *                          updated in fp32 with the same arithmetic (the state leaves exactly as the fp32 call leaves it on the widened table) and
+ *                          rounded back stochastically by nrx_sparse_adam_step_bf16's definition, on (sr_seed, step, table, row * row_mul[t] +
+ *                          row_add[t], col).  step / step_dev, row_mul / row_add: as in nrx_sparse_adam_step_bf16_rows (host arrays of n_tables
+ *                          entries, both NULL: the identity); they are ignored for fp32 tables, where a non-NULL map is an error.
+ * Every product, sum and quotient above is rounded once, as written (no contraction besides the one fma).
+ * ORDER OF THE ROW-WISE SUM S.  It depends on dim only -- not on the launch shape, the row's position in the list, its table, or the alignment of
+ * the buffers -- so a list may be permuted, split over several calls or sharded over ranks and leaves the same bits.  Q = the smallest power of two
+ * with 4 Q >= dim, at most 64.  The columns are cut into chunks of four; chunk j belongs to lane (j % Q) of the row's Q lanes.  Each lane starts from
+ * 0.0f and takes its columns in ASCENDING order, acc = fma(g_k, g_k, acc).  The Q lane sums are then combined by a fixed butterfly, in every step each
+ * lane adding its partner's value to its own:  lane ^ 1;  lane ^ 2;  lane ^ 7 (the mirror inside each 8 lanes);  lane ^ 15 (the mirror inside each 16);
+ * lane ^ 16;  lane ^ 32  -- the first log2(Q) steps of that list.  (Both operands of a step are equal across the lanes they come from, so all lanes
+ * end with the same bits.)  Then s = s + S / (float)dim.
+ * lr_dev (optional, device float[1]) is read in the place of lr (captured loops that follow a schedule); lr_times_weight_decay is a host value.
+ * One call writes the states of up to 32 neighbouring rows into one 128-byte line from different lane groups and blocks: each is a 4-byte store to the
+ * row's own word; no word of another row is read or written. */
+#define NRX_ADAGRAD_ROWWISE 1u
+#define NRX_ADAGRAD_TABLE_BF16 2u
+NRX_API int nrx_sparse_adagrad_step(void* const* tables, float* const* state, int32_t n_tables, int32_t dim, const int64_t* uniq_keys,
+                         const float* grads, int64_t n_unique, const int64_t* n_unique_dev, float lr, const float* lr_dev,
+                         float eps, float lr_times_weight_decay, uint32_t flags, uint64_t sr_seed, int64_t step,
+                         const int64_t* step_dev, const int64_t* row_mul, const int64_t* row_add, void* stream);
+
+/* Exact dense AdamW from row-sparse gradients ("exact-dense mode"). The reference trains every embedding table with one dense
  * torch.optim.AdamW over model.parameters() (src/model/sort/deep/model.py:54-65): every row moves every step.  nrx_rows_mark writes, for every
  * key i = (t << 40 | row) of a unique-key list (negative keys / tables >= n_tables: fillers; row 0: the padding row), slot_maps[t][row] = i --
  * the maps (int32 [rows[t]], all -1 before); nrx_dense_adamw_rows then does ONE AdamW step (torch's arithmetic: decoupled weight decay, bias

@@ -36,6 +36,8 @@ NRX_FEAT_ROW0_IS_DATA = 1
 NRX_FEAT_BAG_CSR = 2
 NRX_FEAT_MANY_PER_ROW = 4
 NRX_FEAT_TABLE_BF16 = 8           # the forward's table is bf16 [rows, dim]
+NRX_ADAGRAD_ROWWISE = 1           # nrx_sparse_adagrad_step flags
+NRX_ADAGRAD_TABLE_BF16 = 2
 
 
 class NrxFeature(C.Structure):
@@ -190,6 +192,8 @@ SIGNATURES = {
                                             C.c_float, C.c_uint64, _i64, _p, _p]),
     "nrx_sparse_adam_step_bf16_rows": (C.c_int, [_p, _p, _p, _i32, _i32, _p, _p, _i64, _p, C.c_float, _p, C.c_float, C.c_float, C.c_float,
                                                  C.c_float, C.c_uint64, _i64, _p, C.POINTER(_i64), C.POINTER(_i64), _p]),
+    "nrx_sparse_adagrad_step": (C.c_int, [_p, _p, _i32, _i32, _p, _p, _i64, _p, C.c_float, _p, C.c_float, C.c_float, C.c_uint32, C.c_uint64,
+                                          _i64, _p, C.POINTER(_i64), C.POINTER(_i64), _p]),
     "nrx_rows_to_dense": (C.c_int, [_p, _i32, _i32, _p, _p, _i64, _p, _i32, _p]),
     "nrx_topk_workspace": (_i64, [_i64, _i64, _i32]),
     "nrx_topk_ip": (C.c_int, [_p, _i64, _i32, _p, _i64, _i32, _p, _p, _p, _p, _p, _p]),

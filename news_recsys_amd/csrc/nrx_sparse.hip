@@ -2696,3 +2696,311 @@ extern "C" int nrx_sparse_adam_step_bf16_rows(uint16_t* const* tables, float* co
     return sparse_adam_bf16_launch("nrx_sparse_adam_step_bf16_rows", row_mul, row_add, tables, exp_avg, exp_avg_sq, n_tables, dim, uniq_keys, grads, n_unique,
                                    n_unique_dev, step_size, step_size_dev, beta1, beta2, eps, lr_times_weight_decay, sr_seed, step, step_dev, stream);
 }
+
+// ---------------------------------------------------------------------------------------------------
+// Fused row-sparse Adagrad on the same unique-row lists (nrx_sparse_adagrad_step; the update rules and the summation order of the
+// row-wise form are written down in nrx_embed.h).  One fp32 accumulator per ELEMENT (state [rows, dim]: torch.optim.Adagrad on sparse
+// gradients) or one per ROW (state [rows]: the mean of the row's squared gradient) instead of Adam's two moments per element.
+// Lane mapping = sparse_adam_kernel's: Q lanes per row chosen from dim, R = 4 rows in flight per lane group, a float4 per lane.  Lane l
+// of a group owns the columns c with (c / 4) % Q == l in BOTH forms (VEC: one 16-byte access per four columns; otherwise element by
+// element), so the row-wise sum of squares has one order per dim, whatever the alignment of the buffers.
+// ---------------------------------------------------------------------------------------------------
+namespace {
+
+struct SparseAdagradArgs {
+    void* table[NRX_MAX_FEATURES];      // fp32 [rows, dim], or (BF16) uint16 patterns
+    float* state[NRX_MAX_FEATURES];     // [rows, dim], or (ROWWISE) [rows]
+    int64_t row_mul[NRX_MAX_FEATURES];  // BF16: the rounding hash sees row * row_mul[t] + row_add[t] ({1, 0}: the key's row)
+    int64_t row_add[NRX_MAX_FEATURES];
+    const int64_t* keys;
+    const float* grads;
+    const int64_t* n_dev;
+    int64_t max_n;
+    int32_t n_tables;
+    int32_t dim;
+    float lr, eps, decay;
+    const float* lr_dev;
+    uint64_t seed;
+    int64_t step;
+    const int64_t* step_dev;
+};
+static_assert(sizeof(SparseAdagradArgs) <= 3584, "kernarg budget");
+
+// (contraction off: the products and sums below round exactly as written, in every instantiation -- the bit-identity of the two forms,
+// of sharded and unsharded runs and of bf16 against fp32 tables rests on it; the one fused operation is the explicit fmaf)
+__device__ __forceinline__ float adagrad_sq(float g, float acc) {
+    return fmaf(g, g, acc);
+}
+__device__ __forceinline__ float adagrad_denom(float s, float eps) {
+#pragma clang fp contract(off)
+    return sqrtf(s) + eps;
+}
+__device__ __forceinline__ float adagrad_w(float g, float w, float denom, float lr, float decay) {
+#pragma clang fp contract(off)
+    const float wd = w * decay;
+    w = w - wd;
+    const float num = lr * g;
+    return w - num / denom;
+}
+
+// Sum over the Q = 2^QLOG2 lanes of a row's group (aligned, contiguous lanes of one wavefront), the result in every lane of the group.  The fixed tree:
+// lane ^ 1, lane ^ 2 (quad permutes), the other quad of each 8 (row_half_mirror), the other half of each 16 (row_mirror), lane ^ 16, lane ^ 32.
+// Every step adds two values that are equal across the lanes they came from, so all lanes of the group hold the same bits afterwards.
+template <int QLOG2>
+__device__ __forceinline__ float adagrad_group_sum(float v) {
+    if (QLOG2 >= 1) v += nrx_dpp<0xB1>(v);
+    if (QLOG2 >= 2) v += nrx_dpp<0x4E>(v);
+    if (QLOG2 >= 3) v += nrx_dpp<0x141>(v);
+    if (QLOG2 >= 4) v += nrx_dpp<0x140>(v);
+    if (QLOG2 >= 5) v += __shfl_xor(v, 16, 64);
+    if (QLOG2 >= 6) v += __shfl_xor(v, 32, 64);
+    return v;
+}
+
+template <bool BF16>
+__device__ __forceinline__ float4 adagrad_load_w4(const void* row, int k) {
+    if (BF16) {
+        const uint2 wb = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(row) + k);
+        return nrx_bf16x4_to_f32(wb.x, wb.y);
+    }
+    return nrx_ldg4(reinterpret_cast<const float*>(row) + k, 0);
+}
+template <bool BF16>
+__device__ __forceinline__ void adagrad_store_w4(void* row, int k, float4 o, uint64_t h) {
+    if (BF16) {
+        uint2 b;
+        b.x = (uint32_t)sr_bf16(o.x, h, k) | ((uint32_t)sr_bf16(o.y, h, k + 1) << 16);
+        b.y = (uint32_t)sr_bf16(o.z, h, k + 2) | ((uint32_t)sr_bf16(o.w, h, k + 3) << 16);
+        *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(row) + k) = b;
+    } else {
+        nrx_stg4(reinterpret_cast<float*>(row) + k, 0, o);
+    }
+}
+template <bool BF16>
+__device__ __forceinline__ float adagrad_load_w(const void* row, int k) {
+    if (BF16) return nrx_bf16_to_f32(reinterpret_cast<const uint16_t*>(row)[k]);
+    return reinterpret_cast<const float*>(row)[k];
+}
+template <bool BF16>
+__device__ __forceinline__ void adagrad_store_w(void* row, int k, float o, uint64_t h) {
+    if (BF16) reinterpret_cast<uint16_t*>(row)[k] = sr_bf16(o, h, k);
+    else reinterpret_cast<float*>(row)[k] = o;
+}
+
+template <int QLOG2, bool VEC, bool ROWWISE, bool BF16>
+__global__ __launch_bounds__(NRX_BLOCK) void sparse_adagrad_kernel(const SparseAdagradArgs args_in_kernarg) {
+    const NRX_CONST SparseAdagradArgs* a = nrx_kernarg<SparseAdagradArgs>();
+    constexpr int Q = 1 << QLOG2;
+    constexpr int TB = NRX_BLOCK / Q;
+    constexpr int R = 4;
+    const int q = threadIdx.x & (Q - 1);
+    const int D = a->dim;
+    const float lr = a->lr_dev != nullptr ? nrx_gconst<float>(a->lr_dev)[0] : a->lr;
+    const float eps = a->eps, decay = a->decay;
+    int64_t n = a->max_n;
+    if (a->n_dev != nullptr) {
+        const int64_t nd = nrx_gconst<int64_t>(a->n_dev)[0];
+        n = nd < n ? nd : n;
+    }
+    const int64_t u0 = ((int64_t)blockIdx.x * TB + (threadIdx.x >> QLOG2)) * R;
+    if (u0 >= n) return;                // (a whole lane group leaves: the cross-lane sums below never read outside their group)
+    uint64_t h_step = 0;
+    if (BF16) {
+        const uint64_t step = a->step_dev != nullptr ? (uint64_t)nrx_gconst<int64_t>(a->step_dev)[0] : (uint64_t)a->step;
+        h_step = sr_mix(sr_mix(a->seed) ^ step);
+    }
+    int64_t key[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) key[r] = u0 + r < n ? nrx_gconst<int64_t>(a->keys)[u0 + r] : -1;
+    char* p[R];
+    float* ps[R];
+    const float* pg[R];
+    uint64_t h[R];
+    bool on[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int64_t t = key[r] >> 40, row = key[r] & ((1ll << 40) - 1);
+        on[r] = key[r] >= 0 && row != 0 && t < a->n_tables;        // padding row / filler keys of a merged list
+        const int64_t tc = on[r] ? t : 0, rc = on[r] ? row : 0;
+        p[r] = reinterpret_cast<char*>(a->table[tc]) + rc * D * (BF16 ? 2 : 4);
+        ps[r] = a->state[tc] + (ROWWISE ? rc : rc * D);
+        pg[r] = a->grads + (u0 + (on[r] ? r : 0)) * (int64_t)D;
+        h[r] = 0;
+        if (BF16) h[r] = sr_mix(sr_mix(h_step ^ (uint64_t)tc) ^ (uint64_t)(rc * a->row_mul[tc] + a->row_add[tc]));
+    }
+    if (ROWWISE) {
+        // pass 1: every lane adds the squares of its columns in ascending order, the group's lanes are combined by the fixed tree.  While the
+        // row fits one float4 per lane (dim <= 4 Q: every dim up to 256) the gradient stays in registers for pass 2.
+        const bool once = QLOG2 < 6 || D <= 4 * Q;     // (Q < 64 is chosen with 4 Q >= dim)
+        float4 g0[R];
+        float s_old[R], acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            s_old[r] = ps[r][0];
+            acc[r] = 0.f;
+            g0[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        if (VEC) {
+            if (q * 4 < D) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) g0[r] = nrx_ldg4(pg[r] + q * 4, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                acc[r] = adagrad_sq(g0[r].w, adagrad_sq(g0[r].z, adagrad_sq(g0[r].y, adagrad_sq(g0[r].x, 0.f))));      // (zeros beyond dim add nothing)
+            for (int k = q * 4 + 4 * Q; k < D; k += 4 * Q) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const float4 g = nrx_ldg4(pg[r] + k, 0);
+                    acc[r] = adagrad_sq(g.w, adagrad_sq(g.z, adagrad_sq(g.y, adagrad_sq(g.x, acc[r]))));
+                }
+            }
+        } else {
+            for (int k0 = q * 4; k0 < D; k0 += 4 * Q) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    if (k0 + c < D) {
+#pragma unroll
+                        for (int r = 0; r < R; ++r) acc[r] = adagrad_sq(pg[r][k0 + c], acc[r]);
+                    }
+                }
+            }
+        }
+        float denom[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const float tot = adagrad_group_sum<QLOG2>(acc[r]);
+            const float s_new = s_old[r] + tot / (float)D;
+            denom[r] = adagrad_denom(s_new, eps);
+            if (on[r] && q == 0) ps[r][0] = s_new;          // a 4-byte store to the row's own word: the neighbours in its 128-byte line are other rows'
+        }
+        if (VEC) {
+            for (int k = q * 4; k < D; k += 4 * Q) {
+                float4 g[R], w[R];
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    g[r] = once ? g0[r] : nrx_ldg4(pg[r] + k, 0);
+                    w[r] = adagrad_load_w4<BF16>(p[r], k);
+                }
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    if (on[r]) {
+                        float4 o;
+                        o.x = adagrad_w(g[r].x, w[r].x, denom[r], lr, decay);
+                        o.y = adagrad_w(g[r].y, w[r].y, denom[r], lr, decay);
+                        o.z = adagrad_w(g[r].z, w[r].z, denom[r], lr, decay);
+                        o.w = adagrad_w(g[r].w, w[r].w, denom[r], lr, decay);
+                        adagrad_store_w4<BF16>(p[r], k, o, h[r]);
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if (!on[r]) continue;
+                for (int k0 = q * 4; k0 < D; k0 += 4 * Q)
+                    for (int k = k0; k < k0 + 4 && k < D; ++k)
+                        adagrad_store_w<BF16>(p[r], k, adagrad_w(pg[r][k], adagrad_load_w<BF16>(p[r], k), denom[r], lr, decay), h[r]);
+            }
+        }
+    } else if (VEC) {
+        for (int k = q * 4; k < D; k += 4 * Q) {
+            float4 g[R], w[R], s[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                g[r] = nrx_ldg4(pg[r] + k, 0);
+                w[r] = adagrad_load_w4<BF16>(p[r], k);
+                s[r] = nrx_ldg4(ps[r] + k, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if (on[r]) {
+                    float4 o;
+                    s[r].x = adagrad_sq(g[r].x, s[r].x); o.x = adagrad_w(g[r].x, w[r].x, adagrad_denom(s[r].x, eps), lr, decay);
+                    s[r].y = adagrad_sq(g[r].y, s[r].y); o.y = adagrad_w(g[r].y, w[r].y, adagrad_denom(s[r].y, eps), lr, decay);
+                    s[r].z = adagrad_sq(g[r].z, s[r].z); o.z = adagrad_w(g[r].z, w[r].z, adagrad_denom(s[r].z, eps), lr, decay);
+                    s[r].w = adagrad_sq(g[r].w, s[r].w); o.w = adagrad_w(g[r].w, w[r].w, adagrad_denom(s[r].w, eps), lr, decay);
+                    nrx_stg4(ps[r] + k, 0, s[r]);
+                    adagrad_store_w4<BF16>(p[r], k, o, h[r]);
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (!on[r]) continue;
+            for (int k0 = q * 4; k0 < D; k0 += 4 * Q)
+                for (int k = k0; k < k0 + 4 && k < D; ++k) {
+                    const float g = pg[r][k], s = adagrad_sq(g, ps[r][k]);
+                    ps[r][k] = s;
+                    adagrad_store_w<BF16>(p[r], k, adagrad_w(g, adagrad_load_w<BF16>(p[r], k), adagrad_denom(s, eps), lr, decay), h[r]);
+                }
+        }
+    }
+}
+
+template <bool ROWWISE, bool BF16>
+void sparse_adagrad_launch(int ql, bool vec, unsigned grid, hipStream_t st, const SparseAdagradArgs& a) {
+#define NRX_AG(QL_) if (vec) hipLaunchKernelGGL((sparse_adagrad_kernel<QL_, true, ROWWISE, BF16>), dim3(grid), dim3(NRX_BLOCK), 0, st, a); \
+                    else hipLaunchKernelGGL((sparse_adagrad_kernel<QL_, false, ROWWISE, BF16>), dim3(grid), dim3(NRX_BLOCK), 0, st, a)
+    switch (ql) {
+        case 0: NRX_AG(0); break; case 1: NRX_AG(1); break; case 2: NRX_AG(2); break; case 3: NRX_AG(3); break;
+        case 4: NRX_AG(4); break; case 5: NRX_AG(5); break; default: NRX_AG(6); break;
+    }
+#undef NRX_AG
+}
+
+}  // namespace
+
+extern "C" int nrx_sparse_adagrad_step(void* const* tables, float* const* state, int32_t n_tables, int32_t dim, const int64_t* uniq_keys,
+                                       const float* grads, int64_t n_unique, const int64_t* n_unique_dev, float lr, const float* lr_dev,
+                                       float eps, float lr_times_weight_decay, uint32_t flags, uint64_t sr_seed, int64_t step,
+                                       const int64_t* step_dev, const int64_t* row_mul, const int64_t* row_add, void* stream) {
+    NRX_TRACE();
+    NRX_REQUIRE(n_tables >= 1 && n_tables <= NRX_MAX_FEATURES && dim >= 1 && n_unique >= 0, "nrx_sparse_adagrad_step: bad argument");
+    NRX_REQUIRE((flags & ~(uint32_t)(NRX_ADAGRAD_ROWWISE | NRX_ADAGRAD_TABLE_BF16)) == 0, "nrx_sparse_adagrad_step: unknown flag bits 0x%x", flags);
+    NRX_REQUIRE((row_mul == nullptr) == (row_add == nullptr), "nrx_sparse_adagrad_step: row_mul and row_add come together (both null: identity)");
+    const bool rowwise = (flags & NRX_ADAGRAD_ROWWISE) != 0, bf16 = (flags & NRX_ADAGRAD_TABLE_BF16) != 0;
+    NRX_REQUIRE(bf16 || row_mul == nullptr, "nrx_sparse_adagrad_step: row_mul / row_add belong to bf16 tables (NRX_ADAGRAD_TABLE_BF16)");
+    if (n_unique == 0) return NRX_OK;
+    NRX_REQUIRE(tables && state && uniq_keys && grads, "nrx_sparse_adagrad_step: null buffer");
+    SparseAdagradArgs a;
+    memset(a.row_mul, 0, sizeof(a.row_mul));
+    memset(a.row_add, 0, sizeof(a.row_add));
+    bool vec = (dim & 3) == 0 && nrx_aligned16(grads);
+    for (int t = 0; t < n_tables; ++t) {
+        NRX_REQUIRE(tables[t] && state[t], "nrx_sparse_adagrad_step: table %d: null pointer", t);
+        NRX_REQUIRE((reinterpret_cast<uintptr_t>(tables[t]) & (bf16 ? 1u : 3u)) == 0 && (reinterpret_cast<uintptr_t>(state[t]) & 3u) == 0,
+                    "nrx_sparse_adagrad_step: table %d: misaligned pointer", t);
+        a.table[t] = tables[t];
+        a.state[t] = state[t];
+        a.row_mul[t] = row_mul != nullptr ? row_mul[t] : 1;
+        a.row_add[t] = row_add != nullptr ? row_add[t] : 0;
+        vec = vec && (reinterpret_cast<uintptr_t>(tables[t]) & (bf16 ? 7u : 15u)) == 0 && (rowwise || nrx_aligned16(state[t]));
+    }
+    a.keys = uniq_keys;
+    a.grads = grads;
+    a.n_dev = n_unique_dev;
+    a.max_n = n_unique;
+    a.n_tables = n_tables;
+    a.dim = dim;
+    a.lr = lr;
+    a.lr_dev = lr_dev;
+    a.eps = eps;
+    a.decay = lr_times_weight_decay;
+    a.seed = sr_seed;
+    a.step = step;
+    a.step_dev = step_dev;
+    int ql = 0;
+    while ((4 << ql) < dim && ql < 6) ++ql;
+    const int tb = NRX_BLOCK >> ql;
+    const int64_t groups = (n_unique + 3) / 4;                   // 4 rows per lane group
+    const unsigned grid = (unsigned)((groups + tb - 1) / tb);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (rowwise && bf16) sparse_adagrad_launch<true, true>(ql, vec, grid, st, a);
+    else if (rowwise) sparse_adagrad_launch<true, false>(ql, vec, grid, st, a);
+    else if (bf16) sparse_adagrad_launch<false, true>(ql, vec, grid, st, a);
+    else sparse_adagrad_launch<false, false>(ql, vec, grid, st, a);
+    NRX_LAUNCH_CHECK("nrx_sparse_adagrad_step");
+    return NRX_OK;
+}

@@ -105,6 +105,20 @@ class BaseModel(LightningModule):
             raise ValueError(f"embeddings.table_dtype: bf16 needs embeddings.sparse_grad: fused (got {e.get('sparse_grad', False)!r}): "
                              "bf16 tables train only through the fused row-sparse optimizer")
         self.sr_seed = int(e.get("sr_seed", 0))
+        # new optional keys: the optimizer of the TABLES in the fused row-sparse mode.  "adam" (default): optim.FusedSparseAdam, two fp32 moments per
+        # element; "adagrad" / "rowwise_adagrad": optim.FusedSparseAdagrad, one fp32 accumulator per element / per ROW -- for tables whose Adam moments
+        # do not fit beside them.  table_lr: the tables' step where it differs from train_hparams.lr (the schedule is scaled by table_lr / lr);
+        # adagrad_eps: the eps of w -= lr * g / (sqrt(s) + eps).  The dense parameters keep AdamW.
+        self.table_optimizer = str(e.get("table_optimizer", "adam")).lower()
+        if self.table_optimizer not in ("adam", "adagrad", "rowwise_adagrad"):
+            raise ValueError(f"embeddings.table_optimizer must be 'adam', 'adagrad' or 'rowwise_adagrad' (got {e.get('table_optimizer')!r})")
+        if self.table_optimizer != "adam" and self.sparse_grad != "fused":
+            raise ValueError(f"embeddings.table_optimizer: {self.table_optimizer} needs embeddings.sparse_grad: fused (got "
+                             f"{e.get('sparse_grad', False)!r}): the Adagrad forms drain the fused row-sparse sink")
+        self.table_lr = None if e.get("table_lr") is None else float(e["table_lr"])
+        if self.table_lr is not None and not self.table_lr > 0:
+            raise ValueError("embeddings.table_lr must be positive")
+        self.adagrad_eps = float(e.get("adagrad_eps", 1e-10))
 
         self.dataset_cfg = self.config.get("dataset", {}) or {}
         self.train_hparams = self.config.get("train_hparams", {}) or {}
@@ -426,7 +440,9 @@ class BaseModel(LightningModule):
                 eng = self._shard_engine
                 row_maps = [arena_row_map(eng.rank, eng.world) if getattr(e, "arena", False) else (1, 0) for e in self.embedding_tables.values()]
             optimizer = SparseDenseAdam(table_params, [p for p in self.parameters() if id(p) not in ids], lr=hp.lr, fused_sink=sink,
-                                        exact=self.sparse_grad == "exact", sr_seed=self.sr_seed, row_maps=row_maps)
+                                        exact=self.sparse_grad == "exact", sr_seed=self.sr_seed, row_maps=row_maps,
+                                        table_optimizer=getattr(self, "table_optimizer", "adam"), table_lr=getattr(self, "table_lr", None),
+                                        adagrad_eps=getattr(self, "adagrad_eps", 1e-10))
         else:
             from ..model_utils.optim import dense_adamw
             optimizer = dense_adamw(self.parameters(), lr=hp.lr, betas=(0.9, 0.999))     # torch.optim.AdamW; its one-pass kernel on the GPU

@@ -28,39 +28,21 @@ def dense_adamw(params, **kw):
     return torch.optim.AdamW(params, **kw)
 
 
-class FusedSparseAdam:
-    """Adam(W) for the embedding tables, fused with the row-sparse backward (SURVEY 8f row 2).  The backward
-    leaves (unique (table,row) keys, summed row gradients, counts) on the device in an ops.SparseGradSink; step()
-    updates exactly those rows of weights and moments with one `nrx_sparse_adam_step` launch per group -- no
-    COO tensors, no host synchronisation, no traffic proportional to the table size.  Update rule =
-    torch.optim.SparseAdam (tested against it) + optional decoupled weight decay on the touched rows.
-    A table that received gradients from several backward groups in one step (DSSM's towers share the news
-    table) gets them merged first, so the step is still ONE Adam update per row.  Tables are identified by tensor
-    identity; their moments are created (zeros) the first time a table shows up in the sink.
+class _SinkTableOptimizer:
+    """What the optimizers that drain an ops.SparseGradSink share: tables identified by tensor identity and registered on first appearance (or, bf16, in
+    the order of `params`), the launch-local -> optimizer-wide renumbering of an entry's keys, the merge of a table fed by several backward groups into ONE
+    update per row, the row maps of bf16 arenas, and the step / seed bookkeeping of a checkpoint.  A subclass supplies `_add_state(t)` (the state of a
+    newly registered table) and its `step()`."""
+    _NAME = "FusedSparseAdam"        # the class an error message names
 
-    bf16 tables (torch.bfloat16; all tables of the optimizer then) keep fp32 moments and step through
-    `nrx_sparse_adam_step_bf16`: the fp32 update of the widened row, rounded back to bf16 stochastically with bits that
-    depend on (sr_seed, step, table, row, column) only -- sr_seed and the step count are in state_dict(), so a resumed run
-    continues the same rounding stream.  `table` is the table's position in `params`, which bf16 tables therefore require.
-    `row` is the key's row, or -- row_maps -- an affine function of it: a row-sharded bf16 arena (shard_step.make_arena) names a row by
-    its local index, the hash takes the global one (shard_step.arena_row_map), so a sharded run leaves the unsharded run's bit patterns."""
-
-    def __init__(self, sink: "ops.SparseGradSink", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False,
-                 params=None, sr_seed=0, row_maps=None):
-        """capturable=True keeps the step counter and the bias-corrected step size on the device (like
-        torch.optim.Adam(capturable=True)) so step() can be captured in a HIP graph (graph.GraphedStep); lr is
-        then fixed at capture time.  params (optional): the table tensors in a stable order -- state_dict() then
-        keys the moments by position in that list, so a checkpoint restores into a freshly built model.
-        row_maps (optional, bf16 tables): one (row_mul, row_add) per entry of `params` -- the stochastic rounding hashes
-        row * row_mul + row_add; None, or (1, 0) for a table: the key's row itself."""
-        self.sink, self.lr, self.betas, self.eps, self.weight_decay = sink, lr, betas, eps, weight_decay
+    def _init_common(self, sink, lr, capturable, params, sr_seed, row_maps):
+        self.sink, self.lr = sink, lr
         self.capturable = bool(capturable)
         self.params = list(params) if params is not None else None
         self._t_dev = None
         self.t = 0
         self.tables = []         # every table seen so far; position = the table's index in the optimizer's key space
         self._index = {}         # id(tensor) -> position
-        self.moments = []        # (exp_avg, exp_avg_sq) per table
         self._gmaps = {}         # table-list identity -> device map (launch-local table index -> position)
         self._identity = {}      # table-list identity -> that map is the identity
         self._maps = []          # per-table slot maps of the two-list merge (made on first use)
@@ -82,7 +64,7 @@ class FusedSparseAdam:
             return
         row_maps = [(int(m), int(a)) for m, a in row_maps]
         if self.params is None or len(row_maps) != len(self.params):
-            raise ValueError("FusedSparseAdam: row_maps needs params=<the table list> and one (row_mul, row_add) per table of it")
+            raise ValueError(f"{self._NAME}: row_maps needs params=<the table list> and one (row_mul, row_add) per table of it")
         self.row_maps = row_maps
 
     def _register(self, t: torch.Tensor) -> int:
@@ -90,15 +72,12 @@ class FusedSparseAdam:
         if i is None:
             if t.dtype is torch.bfloat16 and (self.params is None or not any(p is t for p in self.params)):
                 # positions by first appearance in the sink would make the rounding stream depend on the batch order of a run
-                raise ValueError("FusedSparseAdam: bf16 tables need params=<the table list>: their positions in it name them in the "
+                raise ValueError(f"{self._NAME}: bf16 tables need params=<the table list>: their positions in it name them in the "
                                  "stochastic-rounding hash, which a resumed run must reproduce")
             i = len(self.tables)
             self._index[id(t)] = i
             self.tables.append(t)
-            # both moments of a row side by side ([rows, 2, D]; exp_avg / exp_avg_sq are its two views): the update is a random
-            # read-modify-write of (w, m, v) and every 64-byte access costs a 128-byte fetch -- adjacent, m and v share one
-            mv = torch.zeros((t.shape[0], 2, t.shape[1]), dtype=torch.float32 if t.dtype is torch.bfloat16 else t.dtype, device=t.device)
-            self.moments.append((mv[:, 0], mv[:, 1]))
+            self._add_state(t)
         return i
 
     def _global_keys(self, e):
@@ -138,6 +117,104 @@ class FusedSparseAdam:
         merged_keys[seg] = skeys
         return merged_keys, merged_vals
 
+    def _pending_by_dim(self):
+        """The sink's entries as {dim: [(keys in the optimizer's numbering, values)]} (registers the tables an entry names)."""
+        by_dim = {}
+        for e in self.sink.pending:
+            by_dim.setdefault(e["dim"], []).append((self._global_keys(e), e["values"]))
+        return by_dim
+
+    def _update_merged(self, lib, by_dim, update):
+        """update(dim, keys, values) on every list of by_dim, after making the lists of one dim disjoint: a table fed by several backward groups in one
+        step gets ONE update per row."""
+        n = len(self.tables)
+        for dim, lst in by_dim.items():
+            if len(lst) == 1:
+                update(dim, *lst[0])
+            elif len(lst) == 2 and self.pair_merge:
+                # one table fed by two backward groups (DSSM's towers share the news table): ONE update per row.  List A is marked in per-table
+                # slot maps, the pairs of B that A also holds are added into A's rows and blanked (nrx_rows_merge), A is unmarked; the two lists
+                # are then disjoint: three small launches instead of a device sort + segment sums over the concatenation
+                (ka, va), (kb, vb) = lst
+                stream = torch.cuda.current_stream(ka.device).cuda_stream
+                maps = self._slot_maps()
+                rows = (C.c_int64 * n)(*[t.shape[0] for t in self.tables])
+                ops.check(lib.nrx_rows_mark(ka.data_ptr(), ka.numel(), None, maps, rows, n, 0, stream), "nrx_rows_mark")
+                ops.check(lib.nrx_rows_merge(kb.data_ptr(), vb.data_ptr(), kb.numel(), None, va.data_ptr(), maps, rows, n, dim, stream), "nrx_rows_merge")
+                ops.check(lib.nrx_rows_mark(ka.data_ptr(), ka.numel(), None, maps, rows, n, 1, stream), "nrx_rows_mark")
+                update(dim, ka, va)
+                update(dim, kb, vb)
+            else:
+                update(dim, *self._merge(torch.cat([k for k, _ in lst]), torch.cat([v for _, v in lst])))
+
+    def _hash_row_maps(self, n):
+        """(row_mul, row_add) host arrays in the optimizer's table order for the rounding hash of bf16 tables, or (None, None): the identity."""
+        if self.row_maps is None or all(m == (1, 0) for m in self.row_maps):
+            return None, None
+        maps = [self.row_maps[self._stable_index(t)] for t in self.tables]      # (bf16 tables are all in params: _register)
+        return (C.c_int64 * n)(*[m for m, _ in maps]), (C.c_int64 * n)(*[a for _, a in maps])
+
+    def _slot_maps(self):
+        """int32 [rows] per table, all -1 between uses (nrx_rows_mark / nrx_rows_merge): made when a step first needs them."""
+        while len(self._maps) < len(self.tables):
+            t = self.tables[len(self._maps)]
+            self._maps.append(torch.full((t.shape[0],), -1, dtype=torch.int32, device=t.device))
+        return (C.c_void_p * len(self._maps))(*[m.data_ptr() for m in self._maps])
+
+    def zero_grad(self, set_to_none: bool = True):
+        self.sink.clear()
+
+    def _stable_index(self, t):
+        if self.params is not None:
+            for i, p in enumerate(self.params):
+                if p is t:
+                    return i
+        return None
+
+    def _check_saved_key(self, key, what):
+        """A checkpoint names a table by its position in `params`: refuse the ones it could not name, and a `params` that does not cover the key."""
+        if isinstance(key, str):
+            raise ValueError(f"{self._NAME}.load_state_dict: the checkpoint holds {what} of a table that was not in "
+                             "`params` when it was saved; construct the optimizer with params=<the table list>")
+        if self.params is None or not 0 <= key < len(self.params):
+            raise ValueError(f"{self._NAME}.load_state_dict needs params=<the same table list as at save time>")
+
+
+class FusedSparseAdam(_SinkTableOptimizer):
+    """Adam(W) for the embedding tables, fused with the row-sparse backward (SURVEY 8f row 2).  The backward
+    leaves (unique (table,row) keys, summed row gradients, counts) on the device in an ops.SparseGradSink; step()
+    updates exactly those rows of weights and moments with one `nrx_sparse_adam_step` launch per group -- no
+    COO tensors, no host synchronisation, no traffic proportional to the table size.  Update rule =
+    torch.optim.SparseAdam (tested against it) + optional decoupled weight decay on the touched rows.
+    A table that received gradients from several backward groups in one step (DSSM's towers share the news
+    table) gets them merged first, so the step is still ONE Adam update per row.  Tables are identified by tensor
+    identity; their moments are created (zeros) the first time a table shows up in the sink.
+
+    bf16 tables (torch.bfloat16; all tables of the optimizer then) keep fp32 moments and step through
+    `nrx_sparse_adam_step_bf16`: the fp32 update of the widened row, rounded back to bf16 stochastically with bits that
+    depend on (sr_seed, step, table, row, column) only -- sr_seed and the step count are in state_dict(), so a resumed run
+    continues the same rounding stream.  `table` is the table's position in `params`, which bf16 tables therefore require.
+    `row` is the key's row, or -- row_maps -- an affine function of it: a row-sharded bf16 arena (shard_step.make_arena) names a row by
+    its local index, the hash takes the global one (shard_step.arena_row_map), so a sharded run leaves the unsharded run's bit patterns."""
+
+    def __init__(self, sink: "ops.SparseGradSink", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False,
+                 params=None, sr_seed=0, row_maps=None):
+        """capturable=True keeps the step counter and the bias-corrected step size on the device (like
+        torch.optim.Adam(capturable=True)) so step() can be captured in a HIP graph (graph.GraphedStep); lr is
+        then fixed at capture time.  params (optional): the table tensors in a stable order -- state_dict() then
+        keys the moments by position in that list, so a checkpoint restores into a freshly built model.
+        row_maps (optional, bf16 tables): one (row_mul, row_add) per entry of `params` -- the stochastic rounding hashes
+        row * row_mul + row_add; None, or (1, 0) for a table: the key's row itself."""
+        self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
+        self.moments = []        # (exp_avg, exp_avg_sq) per table
+        self._init_common(sink, lr, capturable, params, sr_seed, row_maps)
+
+    def _add_state(self, t):
+        # both moments of a row side by side ([rows, 2, D]; exp_avg / exp_avg_sq are its two views): the update is a random
+        # read-modify-write of (w, m, v) and every 64-byte access costs a 128-byte fetch -- adjacent, m and v share one
+        mv = torch.zeros((t.shape[0], 2, t.shape[1]), dtype=torch.float32 if t.dtype is torch.bfloat16 else t.dtype, device=t.device)
+        self.moments.append((mv[:, 0], mv[:, 1]))
+
     @torch.no_grad()
     def step(self):
         if not self.sink.pending:
@@ -153,9 +230,7 @@ class FusedSparseAdam:
                 self._t_dev = torch.zeros((), dtype=torch.float64, device=dev)
             self._t_dev += 1
             ss_dev = (self.lr * torch.sqrt(1.0 - b2 ** self._t_dev) / (1.0 - b1 ** self._t_dev)).to(torch.float32).reshape(1)
-        by_dim = {}
-        for e in self.sink.pending:
-            by_dim.setdefault(e["dim"], []).append((self._global_keys(e), e["values"]))
+        by_dim = self._pending_by_dim()
         n = len(self.tables)
         if n > _lib.NRX_MAX_FEATURES:
             raise NotImplementedError("FusedSparseAdam: more than 64 distinct tables")
@@ -167,11 +242,8 @@ class FusedSparseAdam:
             raise NotImplementedError("FusedSparseAdam: bf16 and fp32 tables in one optimizer")
         # the rounding stream's step index: the host count, or (capturable) the device count a captured loop advances
         step_dev = self._t_dev.to(torch.int64).reshape(1) if (n_bf16 and self._t_dev is not None) else None
-        rmul = radd = None
-        if n_bf16 and self.row_maps is not None and any(m != (1, 0) for m in self.row_maps):
-            maps = [self.row_maps[self._stable_index(t)] for t in self.tables]      # (bf16 tables are all in params: _register)
-            rmul, radd = (C.c_int64 * n)(*[m for m, _ in maps]), (C.c_int64 * n)(*[a for _, a in maps])
-        def adam(keys, vals):
+        rmul, radd = self._hash_row_maps(n) if n_bf16 else (None, None)
+        def adam(dim, keys, vals):
             if rmul is not None:
                 ops.check(lib.nrx_sparse_adam_step_bf16_rows(tp, mp, vp, n, dim, keys.data_ptr(), vals.data_ptr(), keys.numel(), None,
                                                              step_size, ss_dev.data_ptr() if ss_dev is not None else None, b1, b2, self.eps,
@@ -191,44 +263,10 @@ class FusedSparseAdam:
                                                self.lr * self.weight_decay,
                                                torch.cuda.current_stream(keys.device).cuda_stream), "nrx_sparse_adam_step")
 
-        for dim, lst in by_dim.items():
-            if len(lst) == 1:
-                adam(*lst[0])
-            elif len(lst) == 2 and self.pair_merge:
-                # one table fed by two backward groups (DSSM's towers share the news table): ONE update per row.  List A is marked in per-table
-                # slot maps, the pairs of B that A also holds are added into A's rows and blanked (nrx_rows_merge), A is unmarked; the two lists
-                # are then disjoint: three small launches instead of a device sort + segment sums over the concatenation
-                (ka, va), (kb, vb) = lst
-                stream = torch.cuda.current_stream(ka.device).cuda_stream
-                maps = self._slot_maps()
-                rows = (C.c_int64 * n)(*[t.shape[0] for t in self.tables])
-                ops.check(lib.nrx_rows_mark(ka.data_ptr(), ka.numel(), None, maps, rows, n, 0, stream), "nrx_rows_mark")
-                ops.check(lib.nrx_rows_merge(kb.data_ptr(), vb.data_ptr(), kb.numel(), None, va.data_ptr(), maps, rows, n, dim, stream), "nrx_rows_merge")
-                ops.check(lib.nrx_rows_mark(ka.data_ptr(), ka.numel(), None, maps, rows, n, 1, stream), "nrx_rows_mark")
-                adam(ka, va)
-                adam(kb, vb)
-            else:
-                adam(*self._merge(torch.cat([k for k, _ in lst]), torch.cat([v for _, v in lst])))
-        self.sink.clear()
-
-    def _slot_maps(self):
-        """int32 [rows] per table, all -1 between uses (nrx_rows_mark / nrx_rows_merge): made when a step first needs them."""
-        while len(self._maps) < len(self.tables):
-            t = self.tables[len(self._maps)]
-            self._maps.append(torch.full((t.shape[0],), -1, dtype=torch.int32, device=t.device))
-        return (C.c_void_p * len(self._maps))(*[m.data_ptr() for m in self._maps])
-
-    def zero_grad(self, set_to_none: bool = True):
+        self._update_merged(lib, by_dim, adam)
         self.sink.clear()
 
     # ---- checkpointing: step count + both moments of every table that has been updated so far
-    def _stable_index(self, t):
-        if self.params is not None:
-            for i, p in enumerate(self.params):
-                if p is t:
-                    return i
-        return None
-
     def state_dict(self):
         tables = {}
         for pos, t in enumerate(self.tables):
@@ -250,11 +288,7 @@ class FusedSparseAdam:
         if sd.get("t_dev") is not None and self.capturable and self.params:
             self._t_dev = torch.tensor(sd["t_dev"], dtype=torch.float64, device=self.params[0].device)
         for key, mv in sd["tables"].items():
-            if isinstance(key, str):
-                raise ValueError("FusedSparseAdam.load_state_dict: the checkpoint holds moments of a table that was not in "
-                                 "`params` when it was saved; construct the optimizer with params=<the table list>")
-            if self.params is None or not 0 <= key < len(self.params):
-                raise ValueError("FusedSparseAdam.load_state_dict needs params=<the same table list as at save time>")
+            self._check_saved_key(key, "moments")
             pos = self._register(self.params[key])
             m, v = self.moments[pos]
             m.copy_(mv["exp_avg"])
@@ -269,6 +303,96 @@ class FusedSparseAdam:
             # (ExactDenseAdamW) a checkpoint written before the per-table step counts existed: every table had moved on every one of the `t`
             # steps -- restarting the tables at step 1 would apply lr / (1 - beta1) to the restored moments and leave torch.optim.AdamW's path
             self._steps = {pos: self.t for pos in range(len(self.tables))}
+
+
+class FusedSparseAdagrad(_SinkTableOptimizer):
+    """Adagrad for the embedding tables, fused with the row-sparse backward like FusedSparseAdam and with its contract (the sink is drained in
+    step(); tables by tensor identity, registered on first appearance; a table fed by two backward groups gets ONE update per row; bf16 tables need
+    `params=` and round stochastically from (sr_seed, step, table, row, column); row_maps for bf16 arenas) -- with ONE fp32 accumulator per row
+    (rowwise=True: `s += mean(g^2)` over the row, state [rows]) or per element (rowwise=False: torch.optim.Adagrad on sparse gradients with
+    lr_decay = 0 and initial_accumulator_value = 0, state [rows, dim]) where Adam keeps two moments per element:  `w -= lr * g / (sqrt(s) + eps)`,
+    after the optional decoupled decay `w -= w * lr * weight_decay` of the touched rows.  One `nrx_sparse_adagrad_step` launch per list.
+    The reference trains the tables with dense AdamW: like `sparse_grad: fused` itself this is an opt-in, documented deviation."""
+    _NAME = "FusedSparseAdagrad"
+
+    def __init__(self, sink: "ops.SparseGradSink", lr=1e-2, eps=1e-10, weight_decay=0.0, rowwise=True, capturable=False, params=None, sr_seed=0,
+                 row_maps=None):
+        """capturable=True keeps the step count (the rounding stream of bf16 tables) and the lr on the device, so step() can be captured in a HIP
+        graph (graph.GraphedStep): a replay advances the count itself, and reads the lr from `lr_dev` -- set_lr() between replays follows a
+        schedule (the decay factor lr * weight_decay is a launch argument, fixed at capture time).  params / sr_seed / row_maps: FusedSparseAdam's."""
+        self.eps, self.weight_decay, self.rowwise = eps, weight_decay, bool(rowwise)
+        self.sums = []           # per table: [rows] (rowwise) or [rows, dim], fp32, zeros at registration
+        self.lr_dev = None
+        self._init_common(sink, lr, capturable, params, sr_seed, row_maps)
+
+    def _add_state(self, t):
+        self.sums.append(torch.zeros((t.shape[0],) if self.rowwise else tuple(t.shape), dtype=torch.float32, device=t.device))
+
+    def set_lr(self, lr):
+        """The step of the next step(): the host value and (capturable) the device word a captured step() reads.  Not to be called inside a capture."""
+        self.lr = float(lr)
+        if self.lr_dev is not None:
+            self.lr_dev.fill_(self.lr)
+
+    @torch.no_grad()
+    def step(self):
+        if not self.sink.pending:
+            return
+        lib = _lib.load()
+        self.t += 1
+        if self.capturable:
+            dev = self.sink.pending[0]["uniq"].device
+            if self._t_dev is None:
+                self._t_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+            if self.lr_dev is None:
+                self.lr_dev = torch.full((1,), float(self.lr), dtype=torch.float32, device=dev)
+            elif not torch.cuda.is_current_stream_capturing():
+                self.lr_dev.fill_(float(self.lr))        # (an eager step follows the host value; a captured one reads the word as a replay finds it)
+            self._t_dev += 1
+        by_dim = self._pending_by_dim()
+        n = len(self.tables)
+        if n > _lib.NRX_MAX_FEATURES:
+            raise NotImplementedError("FusedSparseAdagrad: more than 64 distinct tables")
+        n_bf16 = sum(t.dtype is torch.bfloat16 for t in self.tables)
+        if 0 < n_bf16 < n:
+            raise NotImplementedError("FusedSparseAdagrad: bf16 and fp32 tables in one optimizer")
+        tp = (C.c_void_p * n)(*[t.data_ptr() for t in self.tables])
+        sp = (C.c_void_p * n)(*[s.data_ptr() for s in self.sums])
+        flags = (_lib.NRX_ADAGRAD_ROWWISE if self.rowwise else 0) | (_lib.NRX_ADAGRAD_TABLE_BF16 if n_bf16 else 0)
+        rmul, radd = self._hash_row_maps(n) if n_bf16 else (None, None)
+        lr_dev = self.lr_dev.data_ptr() if self.capturable else None
+        step_dev = self._t_dev.data_ptr() if self.capturable else None
+
+        def adagrad(dim, keys, vals):
+            ops.check(lib.nrx_sparse_adagrad_step(tp, sp, n, dim, keys.data_ptr(), vals.data_ptr(), keys.numel(), None, self.lr, lr_dev, self.eps,
+                                                  self.lr * self.weight_decay, flags, self.sr_seed, self.t, step_dev, rmul, radd,
+                                                  torch.cuda.current_stream(keys.device).cuda_stream), "nrx_sparse_adagrad_step")
+
+        self._update_merged(lib, by_dim, adagrad)
+        self.sink.clear()
+
+    # ---- checkpointing: step count, rounding seed and the accumulators of every table that has been updated so far, by position in `params`
+    def state_dict(self):
+        tables = {}
+        for pos, t in enumerate(self.tables):
+            key = self._stable_index(t)
+            tables[key if key is not None else f"unlisted:{pos}"] = {"sum": self.sums[pos]}
+        return {"t": self.t, "t_dev": None if self._t_dev is None else int(self._t_dev.item()), "tables": tables, "sr_seed": self.sr_seed,
+                "rowwise": self.rowwise}
+
+    def load_state_dict(self, sd):
+        if "rowwise" in sd and bool(sd["rowwise"]) != self.rowwise:
+            raise ValueError(f"FusedSparseAdagrad.load_state_dict: the checkpoint was written with rowwise={bool(sd['rowwise'])}, this optimizer has "
+                             f"rowwise={self.rowwise}")
+        self.t = int(sd["t"])
+        if "sr_seed" in sd:
+            self.sr_seed = int(sd["sr_seed"])
+        self._t_dev = None
+        if sd.get("t_dev") is not None and self.capturable and self.params:
+            self._t_dev = torch.tensor([int(sd["t_dev"])], dtype=torch.int64, device=self.params[0].device)
+        for key, st in sd["tables"].items():
+            self._check_saved_key(key, "accumulators")
+            self.sums[self._register(self.params[key])].copy_(st["sum"])
 
 
 class ExactDenseAdamW(FusedSparseAdam):
@@ -361,13 +485,27 @@ class ExactDenseAdamW(FusedSparseAdam):
         self.sink.clear()
 
 
+TABLE_OPTIMIZERS = ("adam", "adagrad", "rowwise_adagrad")
+
+
 class SparseDenseAdam(torch.optim.Optimizer):
     def __init__(self, sparse_params, dense_params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, fused_sink=None,
-                 capturable=False, exact=False, sr_seed=0, row_maps=None):
+                 capturable=False, exact=False, sr_seed=0, row_maps=None, table_optimizer="adam", table_lr=None, adagrad_eps=1e-10):
         """fused_sink: an ops.SparseGradSink -> the tables are updated by FusedSparseAdam from the sink instead of
         torch.optim.SparseAdam from COO .grad tensors.  exact (with fused_sink): by ExactDenseAdamW -- the reference's dense AdamW over every
-        row, weight decay included, fed from the sink.  row_maps: FusedSparseAdam's (bf16 arenas of the bound sharded step)."""
+        row, weight decay included, fed from the sink.  row_maps: FusedSparseAdam's (bf16 arenas of the bound sharded step).
+        table_optimizer: "adam" (the above), or "adagrad" / "rowwise_adagrad" -- FusedSparseAdagrad(rowwise=...) on the tables (needs fused_sink, not
+        exact; eps = adagrad_eps); the dense parameters keep AdamW.  table_lr: the tables' step where it differs from lr (Adagrad wants a larger one
+        than the dense AdamW): a scheduler's lr is forwarded to the tables scaled by table_lr / lr."""
         sparse_params, dense_params = list(sparse_params), list(dense_params)
+        if table_optimizer not in TABLE_OPTIMIZERS:
+            raise ValueError(f"SparseDenseAdam: table_optimizer must be one of {TABLE_OPTIMIZERS} (got {table_optimizer!r})")
+        if table_optimizer != "adam" and (fused_sink is None or exact):
+            raise ValueError(f"SparseDenseAdam: table_optimizer={table_optimizer!r} needs fused_sink and exact=False (the Adagrad forms drain the "
+                             "row-sparse sink: embeddings.sparse_grad: fused)")
+        if table_lr is not None and not (float(table_lr) > 0 and lr > 0):
+            raise ValueError("SparseDenseAdam: table_lr and lr must be positive")
+        self._table_scale = 1.0 if table_lr is None else float(table_lr) / float(lr)
         groups = [{"params": sparse_params, "sparse": True}]
         if dense_params:
             groups.append({"params": dense_params, "sparse": False})
@@ -380,7 +518,10 @@ class SparseDenseAdam(torch.optim.Optimizer):
             raise TypeError("SparseDenseAdam: bf16 tables train only with the fused sink (torch.optim.SparseAdam needs COO gradients, "
                             "which bf16 tables do not form); use embeddings.sparse_grad: fused")
         self._sparse = (ExactDenseAdamW(fused_sink, sparse_params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable) if exact else
-                        FusedSparseAdam(fused_sink, lr=lr, betas=betas, eps=eps, capturable=capturable, params=sparse_params, sr_seed=sr_seed,
+                        FusedSparseAdagrad(fused_sink, lr=lr * self._table_scale, eps=adagrad_eps, rowwise=table_optimizer == "rowwise_adagrad",
+                                           capturable=capturable, params=sparse_params, sr_seed=sr_seed, row_maps=row_maps)
+                        if table_optimizer != "adam" else
+                        FusedSparseAdam(fused_sink, lr=lr * self._table_scale, betas=betas, eps=eps, capturable=capturable, params=sparse_params, sr_seed=sr_seed,
                                         row_maps=row_maps)
                         if fused_sink is not None
                         else torch.optim.SparseAdam(sparse_params, lr=lr, betas=betas, eps=eps))
@@ -394,8 +535,8 @@ class SparseDenseAdam(torch.optim.Optimizer):
             with torch.enable_grad():         # the closure runs forward + backward
                 loss = closure()
         for g in self.param_groups:           # a scheduler edits self.param_groups: forward the lr
-            if g["sparse"] and isinstance(self._sparse, FusedSparseAdam):
-                self._sparse.lr = g["lr"]
+            if g["sparse"] and isinstance(self._sparse, _SinkTableOptimizer):
+                self._sparse.lr = g["lr"] * self._table_scale
                 continue
             for inner in ((self._sparse,) if g["sparse"] else ((self._dense,) if self._dense else ())):
                 for ig in inner.param_groups:

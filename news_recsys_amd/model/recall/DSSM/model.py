@@ -116,6 +116,9 @@ class DSSM(BaseModel):
         if any(e.weight.dtype is torch.bfloat16 for e in self.embedding_tables.values()):
             raise NotImplementedError("DSSM trains with dense AdamW over every parameter; bf16 tables (embeddings.table_dtype: bf16) "
                                       "serve its forward, inference and retrieval only")
+        if getattr(self, "table_optimizer", "adam") != "adam":
+            raise NotImplementedError("DSSM trains with dense AdamW over every parameter; embeddings.table_optimizer: "
+                                      f"{self.table_optimizer} belongs to the ranking models' fused row-sparse mode")
         from ...model_utils.optim import dense_adamw
         optimizer = dense_adamw(self.parameters(), lr=hp["lr"], betas=(0.9, 0.999))          # torch.optim.AdamW; its one-pass kernel on the GPU
         sched = CosinDecayLR(optimizer, lrs=[hp["lr"], hp["min_lr"]], milestones=list(hp["lr_milestones"]))

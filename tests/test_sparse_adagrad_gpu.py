@@ -24,6 +24,7 @@ from news_recsys_amd import _lib, ops, shard_step
 from news_recsys_amd._lib import NRX_ADAGRAD_ROWWISE, NRX_ADAGRAD_TABLE_BF16, NRX_FEAT_TABLE_BF16, NRX_SPARSE
 from news_recsys_amd.model.model_utils.optim import FusedSparseAdagrad, SparseDenseAdam
 from tests import sr_bf16_ref as SR
+from tests.row_optim_ref import key_list as _key_list          # (n, rng): three tables of ROWS = 40 rows
 from tests.test_fused_sparse_adam_gpu import _setup
 
 pytestmark = pytest.mark.gpu
@@ -129,29 +130,6 @@ def _call(tables, state, dim, keys, grads, flags, n_dev=None, lr=0.05, eps=1e-10
                                           n_dev.data_ptr() if n_dev is not None else None, lr, None, eps, decay, flags, seed, step, None, rmul, radd,
                                           torch.cuda.current_stream().cuda_stream), "nrx_sparse_adagrad_step")
     torch.cuda.synchronize()
-
-
-def _key_list(n, rng):
-    """n entries over three tables of ROWS rows: real keys (consecutive rows of table 1 first: one 128-byte line of the row-wise state is written by
-    several lane groups), -1 and INT64_MAX fillers interleaved, a key with row 0, a key with table 3 (>= n_tables).  From n >= 3 on the LAST entry is a
-    real key that a device-side count of n - 1 must hide."""
-    real = [(1 << 40) | r for r in range(1, ROWS)] + [(0 << 40) | r for r in range(ROWS - 1, 0, -2)] + [(2 << 40) | int(r) for r in rng.permutation(np.arange(1, ROWS))]
-    last = real.pop(3)                       # (table 1, row 4): in the middle of the run of consecutive rows
-    keys, it = [], iter(real)
-    for i in range(n):
-        if n >= 3 and i == n - 1:
-            keys.append(last)
-        elif n > 1 and i % 5 == 1:
-            keys.append(-1)
-        elif i % 7 == 3:
-            keys.append(BIG)
-        elif i == 2:
-            keys.append((1 << 40) | 0)       # the padding row
-        elif i == 4:
-            keys.append((3 << 40) | 5)       # a table the call does not have
-        else:
-            keys.append(next(it, -1))
-    return np.array(keys, dtype=np.int64), (n - 1 if n >= 3 else None)
 
 
 def _restate(w, s, keys, g, rowwise, lr, eps, decay, n_tables=3):

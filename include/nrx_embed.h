@@ -393,6 +393,39 @@ NRX_API int nrx_sparse_adagrad_step(void* const* tables, float* const* state, in
                          float eps, float lr_times_weight_decay, uint32_t flags, uint64_t sr_seed, int64_t step,
                          const int64_t* step_dev, const int64_t* row_mul, const int64_t* row_add, void* stream);
 
+/* Global gradient norm of row-sparse gradient lists, for clipping (torch.nn.utils.clip_grad_norm_ sees .grad tensors only; the lists of an
+ * ops.SparseGradSink never become one).  Everything below is integer or fixed-order double arithmetic: the result is the same bits run to run and
+ * however the rows are ordered, split over calls or sharded over ranks.
+ * LIVE KEY.  As in nrx_sparse_adagrad_step: key (t << 40) | row, not negative, not INT64_MAX, t < n_tables, row != 0, index below *n_dev when that is
+ * given -- and bit t of the host mask `skip_tables` clear (tables this caller must not count: a replicated table on the ranks other than 0).  Rows of
+ * keys that are not live contribute nothing, whatever their values hold (the padding row's slot may hold non-zero values).
+ * ROW SUM, in double; the order depends on dim only.  Q = the smallest power of two with 4 Q >= dim, at most 64.  The columns are cut into chunks of
+ * four; chunk j belongs to lane (j % Q).  A lane starts from 0.0 and takes its columns in ascending order, acc = acc + (double)g * (double)g (the
+ * product of two floats is exact in double).  The Q lane sums are combined by the balanced tree x[l] = x[l] + x[l ^ s] for s = 1, 2, 4, ...  Then
+ * s32 = (float)S, round to nearest even.
+ * BINS: uint64_t bins[258], integer adds only.  b = bits(s32) & 0x7FFFFFFF, e = b >> 23, m = b & 0x7FFFFF:
+ *   e == 0               bins[1] += m                 (zero and the float denormals: the scale of exponent 1)
+ *   1 <= e <= 254        bins[e] += m | 0x800000
+ *   e == 255, m == 0     bins[256] += 1               (infinite: the row sum overflowed a float, or an element was infinite)
+ *   e == 255, m != 0     bins[257] += 1               (NaN)
+ * Integer addition is associative, so the bins are a function of the SET of live rows: permuting a list, splitting it over calls, or sharding it over
+ * ranks and adding the ranks' bins as int64 gives the same words (2^24 per row x 2^31 rows x 8 ranks fits 64 bits).  bins[0] and bins[255] stay zero.
+ * nrx_rows_sqnorm ADDS the live rows of one list (grads [n, dim]) into `bins` (device, 258 words, zeroed by the caller before the first list of a
+ * step or re-armed by the finish launch).
+ * FINISH (nrx_rows_sqnorm_finish, one small launch).  total_sq = the sum over e = 1..254, ascending, of (double)bins[e] * 2^(e - 150) (the
+ * conversion of a word is exact below 2^53 -- some 2^29 rows in one exponent -- and rounds to nearest even above; the scaling by a power of two is
+ * exact, the adds are plain double adds), + *extra_sq_dev when given (the dense parameters' part).  norm = sqrt(total_sq); NaN if bins[257] > 0 or
+ * the extra part is NaN, otherwise +inf if bins[256] > 0.  coef = (float) min(1.0, max_norm / (norm + 1e-6)) in double -- clip_grad_norm_'s formula; a
+ * NaN stays NaN as it does there.  norm_out: device double[1]; coef_out: device float[1]; rearm != 0: the bins are zeroed afterwards (a captured
+ * step replays).  max_norm must be positive.
+ * nrx_rows_scale: values[i] = values[i] * *coef_dev (one rounding) for the n * dim values of a list.  With *coef_dev == 1.0f every block returns
+ * before any load or store of `values`: a step that does not clip pays the norm pass only. */
+NRX_API int nrx_rows_sqnorm(const int64_t* uniq_keys, const float* grads, int64_t n, const int64_t* n_dev, int32_t n_tables, int32_t dim,
+                  uint64_t skip_tables, uint64_t* bins, void* stream);
+NRX_API int nrx_rows_sqnorm_finish(uint64_t* bins, const double* extra_sq_dev, double max_norm, double* norm_out, float* coef_out,
+                  int32_t rearm, void* stream);
+NRX_API int nrx_rows_scale(float* values, int64_t n, int32_t dim, const float* coef_dev, void* stream);
+
 /* Exact dense AdamW from row-sparse gradients ("exact-dense mode"). The reference trains every embedding table with one dense
  * torch.optim.AdamW over model.parameters() (src/model/sort/deep/model.py:54-65): every row moves every step.  nrx_rows_mark writes, for every
  * key i = (t << 40 | row) of a unique-key list (negative keys / tables >= n_tables: fillers; row 0: the padding row), slot_maps[t][row] = i --

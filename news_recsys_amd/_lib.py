@@ -194,6 +194,9 @@ SIGNATURES = {
                                                  C.c_float, C.c_uint64, _i64, _p, C.POINTER(_i64), C.POINTER(_i64), _p]),
     "nrx_sparse_adagrad_step": (C.c_int, [_p, _p, _i32, _i32, _p, _p, _i64, _p, C.c_float, _p, C.c_float, C.c_float, C.c_uint32, C.c_uint64,
                                           _i64, _p, C.POINTER(_i64), C.POINTER(_i64), _p]),
+    "nrx_rows_sqnorm": (C.c_int, [_p, _p, _i64, _p, _i32, _i32, C.c_uint64, _p, _p]),
+    "nrx_rows_sqnorm_finish": (C.c_int, [_p, _p, C.c_double, _p, _p, _i32, _p]),
+    "nrx_rows_scale": (C.c_int, [_p, _i64, _i32, _p, _p]),
     "nrx_rows_to_dense": (C.c_int, [_p, _i32, _i32, _p, _p, _i64, _p, _i32, _p]),
     "nrx_topk_workspace": (_i64, [_i64, _i64, _i32]),
     "nrx_topk_ip": (C.c_int, [_p, _i64, _i32, _p, _i64, _i32, _p, _p, _p, _p, _p, _p]),

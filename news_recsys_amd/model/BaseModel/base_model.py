@@ -122,6 +122,16 @@ class BaseModel(LightningModule):
 
         self.dataset_cfg = self.config.get("dataset", {}) or {}
         self.train_hparams = self.config.get("train_hparams", {}) or {}
+        # new optional key (default absent: no clipping): the bound of the GLOBAL gradient norm -- table rows and dense parameters together -- in the
+        # row-sparse modes, whose table gradients never become .grad tensors (torch.nn.utils.clip_grad_norm_ would see the dense head only)
+        mgn = self.train_hparams.get("max_grad_norm")
+        self.max_grad_norm = None if mgn is None else float(mgn)
+        if self.max_grad_norm is not None:
+            if not self.max_grad_norm > 0:
+                raise ValueError(f"train_hparams.max_grad_norm must be positive (got {mgn!r})")
+            if self.sparse_grad not in ("fused", "exact"):
+                raise ValueError(f"train_hparams.max_grad_norm needs embeddings.sparse_grad: fused | exact (got {e.get('sparse_grad', False)!r}): "
+                                 "in the other modes the tables hold .grad tensors and Trainer(gradient_clip_val=...) clips them")
 
     def _validate_config(self) -> None:
         if not self.out_basedir:
@@ -418,6 +428,32 @@ class BaseModel(LightningModule):
         self.log("train_loss", loss, prog_bar=True, on_epoch=True, on_step=False)
         return loss
 
+    def configure_gradient_clipping(self, optimizer, gradient_clip_val=None, gradient_clip_algorithm=None):
+        """Lightning's hook behind Trainer(gradient_clip_val=...).  In the row-sparse modes (embeddings.sparse_grad: fused | exact) the table gradients
+        sit in the sink, not in .grad: the optimizer clips the GLOBAL norm itself (optim.SparseDenseAdam(max_grad_norm=...)), so the hook hands it
+        the value.  Every other mode holds .grad tensors: Lightning's own clipping, or torch.nn.utils.clip_grad_norm_ without Lightning."""
+        if self.sparse_grad in ("fused", "exact"):
+            if gradient_clip_val is None:
+                return
+            if str(getattr(gradient_clip_algorithm, "value", gradient_clip_algorithm) or "norm").lower() == "value":
+                raise NotImplementedError("gradient_clip_algorithm='value' is not implemented for embeddings.sparse_grad: fused | exact (the "
+                                          "row-sparse table gradients are clipped by their global norm)")
+            opt = getattr(optimizer, "optimizer", optimizer)             # (Lightning hands over its LightningOptimizer wrapper)
+            if not hasattr(opt, "set_max_grad_norm"):
+                raise NotImplementedError(f"gradient_clip_val with embeddings.sparse_grad: {self.sparse_grad} needs the optimizer that "
+                                          f"configure_optimizers() builds (got {type(opt).__name__})")
+            opt.set_max_grad_norm(float(gradient_clip_val))
+            return
+        from ...lightning_shim import HAVE_LIGHTNING
+        if HAVE_LIGHTNING:
+            return super().configure_gradient_clipping(optimizer, gradient_clip_val=gradient_clip_val, gradient_clip_algorithm=gradient_clip_algorithm)
+        if gradient_clip_val is None:
+            return
+        if str(gradient_clip_algorithm or "norm").lower() == "value":
+            torch.nn.utils.clip_grad_value_(self.parameters(), float(gradient_clip_val))
+        else:
+            torch.nn.utils.clip_grad_norm_(self.parameters(), float(gradient_clip_val))
+
     def _ranking_optimizers(self):
         """configure_optimizers of every sort model (e.g. sort/deep/model.py:54-65)."""
         from ..model_utils.lr_schedule import CosinDecayLR
@@ -439,10 +475,20 @@ class BaseModel(LightningModule):
                 from ...shard_step import arena_row_map
                 eng = self._shard_engine
                 row_maps = [arena_row_map(eng.rank, eng.world) if getattr(e, "arena", False) else (1, 0) for e in self.embedding_tables.values()]
+            norm_group, norm_skip = None, None
+            eng = getattr(self, "_shard_engine", None)
+            if eng is not None and eng.world > 1:
+                # the bound sharded step: every rank holds its arenas' rows -- the bins are summed over the ranks -- and the replicated tables' reduced
+                # gradient, the same bits on every rank: rank 0 alone counts it
+                import torch.distributed as dist
+                norm_group = eng.group if eng.group is not None else dist.group.WORLD
+                if eng.rank != 0:
+                    norm_skip = [self.embedding_tables[t].weight for t in getattr(self, "_replicated_tables", ())]
             optimizer = SparseDenseAdam(table_params, [p for p in self.parameters() if id(p) not in ids], lr=hp.lr, fused_sink=sink,
                                         exact=self.sparse_grad == "exact", sr_seed=self.sr_seed, row_maps=row_maps,
                                         table_optimizer=getattr(self, "table_optimizer", "adam"), table_lr=getattr(self, "table_lr", None),
-                                        adagrad_eps=getattr(self, "adagrad_eps", 1e-10))
+                                        adagrad_eps=getattr(self, "adagrad_eps", 1e-10), max_grad_norm=getattr(self, "max_grad_norm", None),
+                                        norm_group=norm_group, norm_skip=norm_skip)
         else:
             from ..model_utils.optim import dense_adamw
             optimizer = dense_adamw(self.parameters(), lr=hp.lr, betas=(0.9, 0.999))     # torch.optim.AdamW; its one-pass kernel on the GPU

@@ -51,6 +51,14 @@ class _SinkTableOptimizer:
         self.row_maps = None
         if row_maps is not None:
             self.set_row_maps(row_maps)
+        # global-norm clipping of the sink's lists (nrx_rows_sqnorm / _finish / nrx_rows_scale; see prepare / finish_norm / apply)
+        self.max_grad_norm = None
+        self.norm_group = None   # a torch.distributed group: the ranks' bins are summed (int64) before the finish launch
+        self.norm_skip = None    # table tensors this rank must not count (a replicated table on the ranks other than 0)
+        self.grad_norm = None    # device double[1] / float[1] of the last clipped step: logging without a host read
+        self.clip_coef = None
+        self._norm_bins = None
+        self._prepared = None
         if self.params is not None and any(t.dtype is torch.bfloat16 for t in self.params):
             # the rounding hash names a table by its position here: pinned to the params order, so a run resumed from a checkpoint
             # (whose load registers the tables in that order) hashes every table as the uninterrupted run does
@@ -124,13 +132,13 @@ class _SinkTableOptimizer:
             by_dim.setdefault(e["dim"], []).append((self._global_keys(e), e["values"]))
         return by_dim
 
-    def _update_merged(self, lib, by_dim, update):
-        """update(dim, keys, values) on every list of by_dim, after making the lists of one dim disjoint: a table fed by several backward groups in one
-        step gets ONE update per row."""
+    def _merge_lists(self, lib, by_dim):
+        """(dim, keys, values) for every list of by_dim, after making the lists of one dim disjoint: a table fed by several backward groups in one
+        step gets ONE gradient per row.  A generator: a dim's merge launches run when the consumer reaches that dim."""
         n = len(self.tables)
         for dim, lst in by_dim.items():
             if len(lst) == 1:
-                update(dim, *lst[0])
+                yield (dim, *lst[0])
             elif len(lst) == 2 and self.pair_merge:
                 # one table fed by two backward groups (DSSM's towers share the news table): ONE update per row.  List A is marked in per-table
                 # slot maps, the pairs of B that A also holds are added into A's rows and blanked (nrx_rows_merge), A is unmarked; the two lists
@@ -142,10 +150,114 @@ class _SinkTableOptimizer:
                 ops.check(lib.nrx_rows_mark(ka.data_ptr(), ka.numel(), None, maps, rows, n, 0, stream), "nrx_rows_mark")
                 ops.check(lib.nrx_rows_merge(kb.data_ptr(), vb.data_ptr(), kb.numel(), None, va.data_ptr(), maps, rows, n, dim, stream), "nrx_rows_merge")
                 ops.check(lib.nrx_rows_mark(ka.data_ptr(), ka.numel(), None, maps, rows, n, 1, stream), "nrx_rows_mark")
-                update(dim, ka, va)
-                update(dim, kb, vb)
+                yield dim, ka, va
+                yield dim, kb, vb
             else:
-                update(dim, *self._merge(torch.cat([k for k, _ in lst]), torch.cat([v for _, v in lst])))
+                yield (dim, *self._merge(torch.cat([k for k, _ in lst]), torch.cat([v for _, v in lst])))
+
+    def _update_merged(self, lib, by_dim, update):
+        """update(dim, keys, values) on every list of by_dim (made disjoint: _merge_lists)."""
+        for dim, keys, vals in self._merge_lists(lib, by_dim):
+            update(dim, keys, vals)
+
+    # ---- global-norm clipping.  step() = prepare() -> finish_norm() -> apply() when max_grad_norm is set, and exactly the unclipped sequence of
+    # library calls when it is None.  SparseDenseAdam drives the three phases itself, with the dense parameters' part in between.
+    def _init_clip(self, max_grad_norm, norm_group, norm_skip):
+        self.set_max_grad_norm(max_grad_norm)
+        self.norm_group = norm_group
+        self.norm_skip = list(norm_skip) if norm_skip is not None else None
+
+    def set_max_grad_norm(self, v):
+        """The global-norm bound of the next step() (None: no clipping, no norm).  A captured step keeps the value it was captured with."""
+        if v is not None and not float(v) > 0:
+            raise ValueError(f"{self._NAME}: max_grad_norm must be positive (got {v!r})")
+        self.max_grad_norm = None if v is None else float(v)
+
+    def _clip_buffers(self, dev):
+        if self._norm_bins is None:
+            self._norm_bins = torch.zeros(258, dtype=torch.int64, device=dev)     # (re-armed by every finish launch)
+            self.grad_norm = torch.zeros(1, dtype=torch.float64, device=dev)
+            self.clip_coef = torch.ones(1, dtype=torch.float32, device=dev)
+
+    def _prepare_lists(self, lib):
+        return list(self._merge_lists(lib, self._pending_by_dim()))
+
+    def _skip_mask(self):
+        """The norm_skip tables as a mask over the optimizer's table positions.  A table is found by identity or by its storage (a bound sharded step
+        holds `weight.data` of an fp32 model: another Python object over the same memory).  One that this step's lists did not register yet is
+        legitimately absent -- as long as `params` knows it; a tensor that is neither registered nor in `params` names no table of this optimizer:
+        counting it on every rank would be silent and wrong, so that is an error."""
+        skip = 0
+        for t in self.norm_skip or ():
+            i = self._index.get(id(t))
+            if i is None:
+                i = next((k for k, reg in enumerate(self.tables) if reg.data_ptr() == t.data_ptr() and reg.shape == t.shape), None)
+            if i is not None:
+                skip |= 1 << i
+            elif self.params is None or not any(p.data_ptr() == t.data_ptr() and p.shape == t.shape for p in self.params):
+                raise ValueError(f"{self._NAME}: a norm_skip tensor {tuple(t.shape)} is none of the tables this optimizer has registered or was "
+                                 "given in `params`: it would be counted on every rank")
+        return skip
+
+    @torch.no_grad()
+    def prepare(self, device=None):
+        """Phase 1 of a clipped step: the sink's lists made disjoint (the norm is the MERGED gradient's: a row fed by two backward groups counts
+        once), and every list's live rows added into the bins.  device: where the bins live when the sink is empty."""
+        lib = _lib.load()
+        lists = self._prepare_lists(lib)
+        self._prepared = lists
+        dev = lists[0][1].device if lists else (device if device is not None else (self.tables[0].device if self.tables else
+                                                                                    (self.params[0].device if self.params else None)))
+        if dev is None:
+            if self.norm_group is not None:     # (the other ranks wait in the bins' all-reduce: this rank must reach it too)
+                raise RuntimeError(f"{self._NAME}: a clipped step over several ranks found no gradient and no table to place the norm's bins by; "
+                                   "construct the optimizer with params=<the table list>")
+            return
+        self._clip_buffers(dev)
+        n = len(self.tables)
+        if lists and n > _lib.NRX_MAX_FEATURES:
+            raise NotImplementedError(f"{self._NAME}: more than 64 distinct tables")
+        skip = self._skip_mask()
+        for dim, keys, vals in lists:
+            ops.check(lib.nrx_rows_sqnorm(keys.data_ptr(), vals.data_ptr(), keys.numel(), None, n, dim, skip, self._norm_bins.data_ptr(),
+                                          torch.cuda.current_stream(keys.device).cuda_stream), "nrx_rows_sqnorm")
+
+    @torch.no_grad()
+    def finish_norm(self, extra_sq=None):
+        """Phase 2: the bins (summed over norm_group as int64 when set) + extra_sq (device double[1]: the dense parameters' squared norm) ->
+        grad_norm and clip_coef on the device; the bins are re-armed.  No host read."""
+        if self._norm_bins is None:
+            return
+        if self.norm_group is not None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{self._NAME}: a clipped step over several ranks cannot be captured in a graph (the all-reduce of the norm's "
+                                   "bins is not captured); capture at world 1 or step eagerly")
+            import torch.distributed as dist
+            dist.all_reduce(self._norm_bins, op=dist.ReduceOp.SUM, group=self.norm_group)
+        ops.check(_lib.load().nrx_rows_sqnorm_finish(self._norm_bins.data_ptr(), extra_sq.data_ptr() if extra_sq is not None else None,
+                                                     float(self.max_grad_norm), self.grad_norm.data_ptr(), self.clip_coef.data_ptr(), 1,
+                                                     torch.cuda.current_stream(self._norm_bins.device).cuda_stream), "nrx_rows_sqnorm_finish")
+
+    @torch.no_grad()
+    def apply(self):
+        """Phase 3: every list scaled by clip_coef (a launch that returns at once where the coefficient is 1), then the update launches."""
+        lists, self._prepared = self._prepared, None
+        if lists is None:
+            raise RuntimeError(f"{self._NAME}.apply() without prepare()")
+        if self._norm_bins is not None:
+            lib = _lib.load()
+            for dim, _, vals in lists:
+                ops.check(lib.nrx_rows_scale(vals.data_ptr(), vals.shape[0], dim, self.clip_coef.data_ptr(),
+                                             torch.cuda.current_stream(vals.device).cuda_stream), "nrx_rows_scale")
+        self._step(lists)
+
+    @torch.no_grad()
+    def step(self):
+        if self.max_grad_norm is None:
+            return self._step(None)
+        self.prepare()
+        self.finish_norm()
+        self.apply()
 
     def _hash_row_maps(self, n):
         """(row_mul, row_add) host arrays in the optimizer's table order for the rounding hash of bf16 tables, or (None, None): the identity."""
@@ -198,16 +310,20 @@ class FusedSparseAdam(_SinkTableOptimizer):
     its local index, the hash takes the global one (shard_step.arena_row_map), so a sharded run leaves the unsharded run's bit patterns."""
 
     def __init__(self, sink: "ops.SparseGradSink", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False,
-                 params=None, sr_seed=0, row_maps=None):
+                 params=None, sr_seed=0, row_maps=None, max_grad_norm=None, norm_group=None, norm_skip=None):
         """capturable=True keeps the step counter and the bias-corrected step size on the device (like
         torch.optim.Adam(capturable=True)) so step() can be captured in a HIP graph (graph.GraphedStep); lr is
         then fixed at capture time.  params (optional): the table tensors in a stable order -- state_dict() then
         keys the moments by position in that list, so a checkpoint restores into a freshly built model.
         row_maps (optional, bf16 tables): one (row_mul, row_add) per entry of `params` -- the stochastic rounding hashes
-        row * row_mul + row_add; None, or (1, 0) for a table: the key's row itself."""
+        row * row_mul + row_add; None, or (1, 0) for a table: the key's row itself.
+        max_grad_norm (optional): step() first scales the sink's gradients so that their global norm (the merged lists' live rows; summed over the
+        ranks of norm_group, without the tables of norm_skip) is at most this -- torch.nn.utils.clip_grad_norm_'s rule, computed on the device
+        (include/nrx_embed.h: nrx_rows_sqnorm); grad_norm / clip_coef hold the last step's values on the device."""
         self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
         self.moments = []        # (exp_avg, exp_avg_sq) per table
         self._init_common(sink, lr, capturable, params, sr_seed, row_maps)
+        self._init_clip(max_grad_norm, norm_group, norm_skip)
 
     def _add_state(self, t):
         # both moments of a row side by side ([rows, 2, D]; exp_avg / exp_avg_sq are its two views): the update is a random
@@ -216,7 +332,8 @@ class FusedSparseAdam(_SinkTableOptimizer):
         self.moments.append((mv[:, 0], mv[:, 1]))
 
     @torch.no_grad()
-    def step(self):
+    def _step(self, lists):
+        """lists: None -- the unclipped step, straight from the sink -- or prepare()'s disjoint (dim, keys, values) lists."""
         if not self.sink.pending:
             return
         lib = _lib.load()
@@ -230,7 +347,7 @@ class FusedSparseAdam(_SinkTableOptimizer):
                 self._t_dev = torch.zeros((), dtype=torch.float64, device=dev)
             self._t_dev += 1
             ss_dev = (self.lr * torch.sqrt(1.0 - b2 ** self._t_dev) / (1.0 - b1 ** self._t_dev)).to(torch.float32).reshape(1)
-        by_dim = self._pending_by_dim()
+        by_dim = self._pending_by_dim() if lists is None else None
         n = len(self.tables)
         if n > _lib.NRX_MAX_FEATURES:
             raise NotImplementedError("FusedSparseAdam: more than 64 distinct tables")
@@ -263,7 +380,11 @@ class FusedSparseAdam(_SinkTableOptimizer):
                                                self.lr * self.weight_decay,
                                                torch.cuda.current_stream(keys.device).cuda_stream), "nrx_sparse_adam_step")
 
-        self._update_merged(lib, by_dim, adam)
+        if lists is None:
+            self._update_merged(lib, by_dim, adam)
+        else:
+            for dim, keys, vals in lists:
+                adam(dim, keys, vals)
         self.sink.clear()
 
     # ---- checkpointing: step count + both moments of every table that has been updated so far
@@ -316,14 +437,16 @@ class FusedSparseAdagrad(_SinkTableOptimizer):
     _NAME = "FusedSparseAdagrad"
 
     def __init__(self, sink: "ops.SparseGradSink", lr=1e-2, eps=1e-10, weight_decay=0.0, rowwise=True, capturable=False, params=None, sr_seed=0,
-                 row_maps=None):
+                 row_maps=None, max_grad_norm=None, norm_group=None, norm_skip=None):
         """capturable=True keeps the step count (the rounding stream of bf16 tables) and the lr on the device, so step() can be captured in a HIP
         graph (graph.GraphedStep): a replay advances the count itself, and reads the lr from `lr_dev` -- set_lr() between replays follows a
-        schedule (the decay factor lr * weight_decay is a launch argument, fixed at capture time).  params / sr_seed / row_maps: FusedSparseAdam's."""
+        schedule (the decay factor lr * weight_decay is a launch argument, fixed at capture time).  params / sr_seed / row_maps and
+        max_grad_norm / norm_group / norm_skip: FusedSparseAdam's."""
         self.eps, self.weight_decay, self.rowwise = eps, weight_decay, bool(rowwise)
         self.sums = []           # per table: [rows] (rowwise) or [rows, dim], fp32, zeros at registration
         self.lr_dev = None
         self._init_common(sink, lr, capturable, params, sr_seed, row_maps)
+        self._init_clip(max_grad_norm, norm_group, norm_skip)
 
     def _add_state(self, t):
         self.sums.append(torch.zeros((t.shape[0],) if self.rowwise else tuple(t.shape), dtype=torch.float32, device=t.device))
@@ -335,7 +458,8 @@ class FusedSparseAdagrad(_SinkTableOptimizer):
             self.lr_dev.fill_(self.lr)
 
     @torch.no_grad()
-    def step(self):
+    def _step(self, lists):
+        """lists: None -- the unclipped step, straight from the sink -- or prepare()'s disjoint (dim, keys, values) lists."""
         if not self.sink.pending:
             return
         lib = _lib.load()
@@ -349,7 +473,7 @@ class FusedSparseAdagrad(_SinkTableOptimizer):
             elif not torch.cuda.is_current_stream_capturing():
                 self.lr_dev.fill_(float(self.lr))        # (an eager step follows the host value; a captured one reads the word as a replay finds it)
             self._t_dev += 1
-        by_dim = self._pending_by_dim()
+        by_dim = self._pending_by_dim() if lists is None else None
         n = len(self.tables)
         if n > _lib.NRX_MAX_FEATURES:
             raise NotImplementedError("FusedSparseAdagrad: more than 64 distinct tables")
@@ -368,7 +492,11 @@ class FusedSparseAdagrad(_SinkTableOptimizer):
                                                   self.lr * self.weight_decay, flags, self.sr_seed, self.t, step_dev, rmul, radd,
                                                   torch.cuda.current_stream(keys.device).cuda_stream), "nrx_sparse_adagrad_step")
 
-        self._update_merged(lib, by_dim, adagrad)
+        if lists is None:
+            self._update_merged(lib, by_dim, adagrad)
+        else:
+            for dim, keys, vals in lists:
+                adagrad(dim, keys, vals)
         self.sink.clear()
 
     # ---- checkpointing: step count, rounding seed and the accumulators of every table that has been updated so far, by position in `params`
@@ -405,8 +533,10 @@ class ExactDenseAdamW(FusedSparseAdam):
     its own step count (capturable=True: one device-side count for all tables, every registered table is streamed every step).
     exp_avg / exp_avg_sq are plain [rows, dim] tensors (torch's layout)."""
 
-    def __init__(self, sink, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, capturable=False):
-        super().__init__(sink, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable, params=list(params))
+    def __init__(self, sink, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, capturable=False, max_grad_norm=None,
+                 norm_group=None, norm_skip=None):
+        super().__init__(sink, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable, params=list(params),
+                         max_grad_norm=max_grad_norm, norm_group=norm_group, norm_skip=norm_skip)
         self.maps = []
         for t in self.params:
             self._register(t)
@@ -423,10 +553,8 @@ class ExactDenseAdamW(FusedSparseAdam):
             self.maps.append(torch.full((t.shape[0],), -1, dtype=torch.int32, device=t.device))
         return i
 
-    @torch.no_grad()
-    def step(self):
-        lib = _lib.load()
-        self.t += 1
+    def _collect(self):
+        """The sink's entries as {dim: [(keys, values)]}, and the positions of the tables a backward launch of the step looked up."""
         by_dim = {}
         touched = set()
         for e in self.sink.pending:
@@ -435,6 +563,31 @@ class ExactDenseAdamW(FusedSparseAdam):
                 i = self._index.get(id(e["tables"][tid]))
                 if i is not None:
                     touched.add(i)
+        return by_dim, touched
+
+    def _one_list(self, lst):
+        if len(lst) == 1:
+            return lst[0]
+        # one table fed by several backward groups: ONE gradient per row
+        return self._merge(torch.cat([kk for kk, _ in lst]), torch.cat([v for _, v in lst]))
+
+    def _prepare_lists(self, lib):
+        by_dim, touched = self._collect()
+        merged = {dim: self._one_list(lst) for dim, lst in by_dim.items()}
+        self._collected = (merged, touched)
+        return [(dim, k, v) for dim, (k, v) in merged.items()]
+
+    @torch.no_grad()
+    def _step(self, lists):
+        """lists: None -- the unclipped step, straight from the sink -- or prepare()'s lists (one per dim, already merged and scaled)."""
+        lib = _lib.load()
+        self.t += 1
+        merged = None
+        if lists is None:
+            by_dim, touched = self._collect()
+        else:
+            merged, touched = self._collected
+            by_dim, self._collected = merged, None
         if self.capturable:
             touched = set(range(len(self.tables)))       # (one device-side step count: every table moves every step)
         steps = getattr(self, "_steps", None)
@@ -467,10 +620,7 @@ class ExactDenseAdamW(FusedSparseAdam):
                 vals = None
                 lst = by_dim.get(dim)
                 if lst:
-                    if len(lst) == 1:
-                        keys, vals = lst[0]
-                    else:       # one table fed by several backward groups: ONE gradient per row
-                        keys, vals = self._merge(torch.cat([kk for kk, _ in lst]), torch.cat([v for _, v in lst]))
+                    keys, vals = lst if merged is not None else self._one_list(lst)
                     ops.check(lib.nrx_rows_mark(keys.data_ptr(), keys.numel(), None, maps_all, rows, n, 0, stream), "nrx_rows_mark")
                 marked[dim] = vals
             vals = marked[dim]
@@ -490,14 +640,23 @@ TABLE_OPTIMIZERS = ("adam", "adagrad", "rowwise_adagrad")
 
 class SparseDenseAdam(torch.optim.Optimizer):
     def __init__(self, sparse_params, dense_params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, fused_sink=None,
-                 capturable=False, exact=False, sr_seed=0, row_maps=None, table_optimizer="adam", table_lr=None, adagrad_eps=1e-10):
+                 capturable=False, exact=False, sr_seed=0, row_maps=None, table_optimizer="adam", table_lr=None, adagrad_eps=1e-10,
+                 max_grad_norm=None, norm_group=None, norm_skip=None):
         """fused_sink: an ops.SparseGradSink -> the tables are updated by FusedSparseAdam from the sink instead of
         torch.optim.SparseAdam from COO .grad tensors.  exact (with fused_sink): by ExactDenseAdamW -- the reference's dense AdamW over every
         row, weight decay included, fed from the sink.  row_maps: FusedSparseAdam's (bf16 arenas of the bound sharded step).
         table_optimizer: "adam" (the above), or "adagrad" / "rowwise_adagrad" -- FusedSparseAdagrad(rowwise=...) on the tables (needs fused_sink, not
         exact; eps = adagrad_eps); the dense parameters keep AdamW.  table_lr: the tables' step where it differs from lr (Adagrad wants a larger one
-        than the dense AdamW): a scheduler's lr is forwarded to the tables scaled by table_lr / lr."""
+        than the dense AdamW): a scheduler's lr is forwarded to the tables scaled by table_lr / lr.
+        max_grad_norm (needs fused_sink): step() clips the GLOBAL gradient norm -- the tables' row-sparse lists in the sink and the dense .grads together
+        -- to it, on the device and without a host read: tables' bins (prepare), the dense part (torch._foreach_norm, squared and summed in double),
+        the all-reduce of the bins over norm_group when set (the dense gradients are already all-reduced: every rank adds the same dense part),
+        finish, the dense .grads and the lists scaled by clip_coef, then both updates.  norm_skip: tables this rank must not count (replicated ones
+        on the ranks other than 0).  grad_norm / clip_coef: device tensors of the last clipped step."""
         sparse_params, dense_params = list(sparse_params), list(dense_params)
+        if max_grad_norm is not None and fused_sink is None:
+            raise ValueError("SparseDenseAdam: max_grad_norm needs fused_sink (embeddings.sparse_grad: fused | exact): the COO and dense-gradient "
+                             "modes hold .grad tensors, which torch.nn.utils.clip_grad_norm_ clips")
         if table_optimizer not in TABLE_OPTIMIZERS:
             raise ValueError(f"SparseDenseAdam: table_optimizer must be one of {TABLE_OPTIMIZERS} (got {table_optimizer!r})")
         if table_optimizer != "adam" and (fused_sink is None or exact):
@@ -527,6 +686,42 @@ class SparseDenseAdam(torch.optim.Optimizer):
                         else torch.optim.SparseAdam(sparse_params, lr=lr, betas=betas, eps=eps))
         self._dense = (torch.optim.AdamW(dense_params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable)
                        if dense_params else None)
+        self._dense_params = dense_params
+        if fused_sink is not None:
+            self._sparse._init_clip(max_grad_norm, norm_group, norm_skip)
+
+    @property
+    def max_grad_norm(self):
+        return getattr(self._sparse, "max_grad_norm", None)
+
+    def set_max_grad_norm(self, v):
+        if not isinstance(self._sparse, _SinkTableOptimizer):
+            raise ValueError("SparseDenseAdam: max_grad_norm needs fused_sink (embeddings.sparse_grad: fused | exact)")
+        self._sparse.set_max_grad_norm(v)
+
+    @property
+    def grad_norm(self):
+        return getattr(self._sparse, "grad_norm", None)
+
+    @property
+    def clip_coef(self):
+        return getattr(self._sparse, "clip_coef", None)
+
+    def _clipped_step(self):
+        sp = self._sparse
+        grads = [p.grad for p in self._dense_params if p.grad is not None]
+        if not grads and not sp.sink.pending and sp.norm_group is None:
+            return                          # (with a norm_group the step goes on: the other ranks wait in the bins' all-reduce)
+        sp.prepare(device=grads[0].device if grads else None)
+        extra = None
+        if grads:
+            extra = torch.stack(torch._foreach_norm(grads)).to(torch.float64).square_().sum().reshape(1)
+        sp.finish_norm(extra)
+        if grads:
+            torch._foreach_mul_(grads, sp.clip_coef[0])
+        sp.apply()
+        if self._dense is not None:
+            self._dense.step()
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -541,6 +736,9 @@ class SparseDenseAdam(torch.optim.Optimizer):
             for inner in ((self._sparse,) if g["sparse"] else ((self._dense,) if self._dense else ())):
                 for ig in inner.param_groups:
                     ig["lr"] = g["lr"]
+        if self.max_grad_norm is not None:
+            self._clipped_step()
+            return loss
         self._sparse.step()
         if self._dense is not None:
             self._dense.step()

@@ -119,6 +119,9 @@ class DSSM(BaseModel):
         if getattr(self, "table_optimizer", "adam") != "adam":
             raise NotImplementedError("DSSM trains with dense AdamW over every parameter; embeddings.table_optimizer: "
                                       f"{self.table_optimizer} belongs to the ranking models' fused row-sparse mode")
+        if getattr(self, "max_grad_norm", None) is not None:
+            raise NotImplementedError("DSSM trains with dense AdamW over every parameter; train_hparams.max_grad_norm belongs to the ranking "
+                                      "models' row-sparse modes (use Trainer(gradient_clip_val=...) or torch.nn.utils.clip_grad_norm_ here)")
         from ...model_utils.optim import dense_adamw
         optimizer = dense_adamw(self.parameters(), lr=hp["lr"], betas=(0.9, 0.999))          # torch.optim.AdamW; its one-pass kernel on the GPU
         sched = CosinDecayLR(optimizer, lrs=[hp["lr"], hp["min_lr"]], milestones=list(hp["lr_milestones"]))

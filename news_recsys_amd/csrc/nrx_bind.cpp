@@ -28,10 +28,12 @@ struct BoundPlan {
     bool use_fm = false;
     int fm_dim = 0;
     fwd_train_fn fwd = nullptr;
-    // what the descriptors were last bound to: every table's data pointer and row count (compared on every call -- a list's
-    // address says nothing, CPython reuses it, and a table in the MIDDLE of the list may be re-allocated or resized)
+    // what the descriptors were last bound to: every table's data pointer, row count and type (compared on every call -- a list's
+    // address says nothing, CPython reuses it, and a table in the MIDDLE of the list may be re-allocated, resized or converted: a freed
+    // fp32 table's address can come back as a bf16 table of the same row count)
     std::vector<const void*> bound_ptr;
     std::vector<int64_t> bound_rows;
+    std::vector<at::ScalarType> bound_type;
     c10::Device device{c10::kCPU};
 
     // slots: sequence of (kind, table, dim, bag_len, out_col, wide_col, fm_field, flags)
@@ -75,15 +77,17 @@ struct BoundPlan {
         }
         bound_ptr.resize((size_t)nt);
         bound_rows.resize((size_t)nt);
+        bound_type.resize((size_t)nt);
         for (Py_ssize_t i = 0; i < nt; ++i) {
             bound_ptr[(size_t)i] = ts[(size_t)i]->data_ptr();
             bound_rows[(size_t)i] = ts[(size_t)i]->size(0);
+            bound_type[(size_t)i] = ts[(size_t)i]->scalar_type();
         }
         if (nt) device = ts[0]->device();
         return true;
     }
 
-    // True when every table of the list is the storage (and row count) the descriptors hold.
+    // True when every table of the list is the storage (and row count, and type) the descriptors hold.
     bool tables_unchanged(PyObject* tables) const {
         const Py_ssize_t nt = PyList_GET_SIZE(tables);
         if ((size_t)nt != bound_ptr.size()) return false;
@@ -91,7 +95,9 @@ struct BoundPlan {
             PyObject* o = PyList_GET_ITEM(tables, i);
             if (!THPVariable_Check(o)) return false;
             const at::Tensor& t = THPVariable_Unpack(o);
-            if (t.dim() != 2 || t.data_ptr() != bound_ptr[(size_t)i] || t.size(0) != bound_rows[(size_t)i]) return false;
+            if (t.dim() != 2 || t.data_ptr() != bound_ptr[(size_t)i] || t.size(0) != bound_rows[(size_t)i] ||
+                t.scalar_type() != bound_type[(size_t)i])
+                return false;
         }
         return true;
     }

@@ -24,6 +24,7 @@ from __future__ import annotations
 
 import json
 import logging
+import operator
 import os
 from typing import Dict, List, Optional, Sequence, Set, Tuple
 
@@ -36,6 +37,9 @@ from ...config import load_config, to_container
 from ...lightning_shim import LightningModule
 
 logger = logging.getLogger("BaseModel")
+
+
+_WEIGHT_OF = operator.itemgetter("weight")          # a table module's current Parameter, out of its _parameters dict
 
 
 class BaseModel(LightningModule):
@@ -55,7 +59,7 @@ class BaseModel(LightningModule):
         self.feature_id_mapper = None
         self._plan_cache: Dict[tuple, Tuple[ops.EmbedPlan, List[str], List[int], List[str]]] = {}
         self._embed_cache: Dict[tuple, tuple] = {}
-        self._first_table: Dict[tuple, str] = {}
+        self._table_probe: Dict[tuple, tuple] = {}       # per _embed_cache entry: (getter of its table modules, the modules, their _parameters dicts)
         self._none_lists: Dict[int, list] = {}
 
     # ------------------------------------------------------------------ config (base_model.py:69-139)
@@ -280,8 +284,16 @@ class BaseModel(LightningModule):
                 if batch[n].dim() != 2 or batch[n].shape[1] != L:
                     ent = None
                     break
-            if ent is not None and tables and tables[0] is not self.embedding_tables[self._first_table[ck]].weight:
-                ent = None                              # the tables were replaced (e.g. shard_model_): rebuild
+            if ent is not None and tables:
+                # the tables were replaced (shard_model_, a vocabulary grown between two epochs, ...): rebuild.  EVERY cached table is compared
+                # with its module's current Parameter -- a table in the middle of the list is replaced as easily as the first.  (The modules
+                # by one itemgetter call and one tuple comparison, their Parameters out of the modules' own dicts: profiles/host_paths.txt)
+                getter, mods, pdicts = self._table_probe[ck]
+                try:
+                    if getter(self._modules["embedding_tables"]._modules) != mods or not all(map(operator.is_, map(_WEIGHT_OF, pdicts), tables)):
+                        ent = None
+                except KeyError:                        # a table module was removed, or holds no `weight` Parameter any more
+                    ent = None
         if ent is None:
             plan, table_names, dims, present = self._plan(batch, feature_names, fm, wide_names)
             if not present:
@@ -295,7 +307,9 @@ class BaseModel(LightningModule):
             any_mask = any(m is not None for m in mask_names)
             ent = (plan, tables, in_names, mask_names if any_mask else None, bag_lens, list(dims), list(present))
             if table_names:
-                self._first_table[ck] = table_names[0]
+                md = self._modules["embedding_tables"]._modules
+                getter = operator.itemgetter(*table_names) if len(table_names) > 1 else (lambda d, _n=table_names[0]: d[_n])
+                self._table_probe[ck] = (getter, getter(md), [md[t]._parameters for t in table_names])
             self._embed_cache[ck] = ent
             mask_names = ent[3]
         inputs = [batch[n] for n in in_names]

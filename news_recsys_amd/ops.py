@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import operator
 import os
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
@@ -396,7 +397,7 @@ def _zero_grad_tables(meta):
     return [buf[o:o + math.prod(shape)].view(shape) for o, (shape, _) in zip(offs, meta)]
 
 
-def _dense_sorted_ok(plan, tables, sparse_grad, B, csr_ok=False) -> bool:
+def _dense_sorted_ok(plan, tables, sparse_grad, B, csr_ok=False, rows_key=None) -> bool:
     """Default (dense-gradient) mode: form the table grads by the sorted reduction + nrx_rows_to_dense?  The sorted path costs a fixed
     ~25 launches (~0.2 ms of host and launch time per step), the atomic scatter ~0.2 us per 1000 lookups: from DENSE_SORTED_MIN lookups
     per launch on (786 k: the C4 tower from B = 15 k) the sorted path is as fast or faster, below it the single atomic launch is
@@ -426,7 +427,7 @@ def _dense_sorted_ok(plan, tables, sparse_grad, B, csr_ok=False) -> bool:
     if DENSE_SMALL_DET and _small_shapes(plan, B):
         return False                     # (every table fed by <= 4096 lookups: the one-launch deterministic kernel's)
     return all(g["all_sparse"] and _group_policy(g, B, len(tables)) is not None and _group_policy(g, B, len(tables)).eligible
-               for g in _sparse_group_cache(plan, tables))
+               for g in _sparse_group_cache(plan, tables, rows_key))
 
 
 # which form produced the dense table gradients, counted per backward launch: "small" (one-launch deterministic kernel), "sorted" (planned
@@ -511,8 +512,9 @@ class _EmbedFn(torch.autograd.Function):
             else:
                 status = torch.zeros(4, dtype=torch.int32, device=dev)
                 sp = status.data_ptr()
-            # (autograd only builds this node when some table requires grad: the field sums are always wanted in training form)
-            done = bp.forward(list(tables), inputs, weights, ld, need_out, sp, _raw_stream(dev), bool(plan.use_fm and need_out))
+            # (the field sums under the ctypes path's own condition: an FM plan whose concat is kept, some table a leaf that trains)
+            done = bp.forward(list(tables), inputs, weights, ld, need_out, sp, _raw_stream(dev),
+                              bool(plan.use_fm and need_out and any(t.requires_grad for t in tables)))
             if type(done) is int:
                 check(done, "nrx_embed_fwd_train")
         if done is not None:
@@ -586,7 +588,8 @@ class _EmbedFn(torch.autograd.Function):
         # NRX_DENSE_BWD=atomic, the launch is being captured (the planner allocates) or a feature reads a routed-row buffer
         # (needs_input_grad follows the grad MODE too: a forward under torch.no_grad() -- leaf tables still say requires_grad -- plans nothing)
         wants_grad = any(ctx.needs_input_grad[7:])
-        ctx.dense_sorted = wants_grad and _dense_sorted_ok(plan, tables, ctx.sparse_grad, B, csr_ok=True)
+        ctx.rows_key = rows_key = _rows_key(tables) if wants_grad else None      # (read once per node: the launch groups of the backward are keyed by it)
+        ctx.dense_sorted = wants_grad and _dense_sorted_ok(plan, tables, ctx.sparse_grad, B, csr_ok=True, rows_key=rows_key)
         if ctx.dense_sorted and any(s.flags & NRX_FEAT_BAG_CSR for s in plan.slots):
             # the forward ran on the CSR form; the backward's planner sorts padded [B, L] lookups (nrx_csr_to_padded: one small launch
             # per bag feature) -- from here on the node only describes the backward
@@ -597,7 +600,7 @@ class _EmbedFn(torch.autograd.Function):
             small = True                 # the sink's one-launch form (nrx_embed_bwd_small_sparse) plans nothing
         if (ctx.sparse_grad or ctx.dense_sorted) and PLAN_AHEAD and B > 0 and not torch.cuda.is_current_stream_capturing() and wants_grad and not small:
             ctx.plans = {}
-            for g_ in _sparse_group_cache(plan, tables):
+            for g_ in _sparse_group_cache(plan, tables, rows_key):
                 fs_ = g_["fs"]
                 pol_ = _group_policy(g_, B, len(tables))
                 if pol_ is not None and pol_.choose() and not PLAN_AHEAD_LDS:
@@ -1033,10 +1036,22 @@ def _bwd_sorted(lib, pl, pmask, arr, n, B, D, g_out, ld, g_wide, wide_ld, n_uniq
     return pl
 
 
-def _sparse_group_cache(plan: EmbedPlan, tables):
-    """Per launch group of the row-sparse backward, built once per (plan, table set): slot indices, the group's sub-plan (its cached
-    descriptor array lives there), table ids / row counts as the ctypes arrays nrx_sparse_plan takes, the placement mask."""
-    key = (len(tables), tables[0].data_ptr() if len(tables) else 0)
+def _rows_key(tables) -> tuple:
+    """Every table's row count (a list comprehension over .shape[0]: the cheapest of the forms tried, profiles/host_paths.txt)."""
+    return tuple([t.shape[0] for t in tables])
+
+
+_DATA_PTR = operator.methodcaller("data_ptr")
+
+
+def _sparse_group_cache(plan: EmbedPlan, tables, key: Optional[tuple] = None):
+    """Per launch group of the row-sparse backward, built once per (plan, row counts of the table set): slot indices, the group's sub-plan
+    (its cached descriptor array lives there), table ids / row counts as the ctypes arrays nrx_sparse_plan takes, the placement mask.
+    Nothing cached here holds a table's address -- only the row counts, which the planner clamps ids by and the policies are sized from: the
+    key is EVERY table's row count (a table in the middle of the list may grow between two epochs; the first table says nothing about it).
+    key: _rows_key(tables) where the caller has it already (an autograd node forms it once for its forward and backward)."""
+    if key is None:
+        key = _rows_key(tables)
     ent = plan.__dict__.get("_sg")
     if ent is None or ent[0] != key:
         groups = []
@@ -1112,7 +1127,7 @@ def _sorted_sparse_grads(ctx, lib, g_out, g_wide, stream, fmg=None, dense_into=N
     dense_ptrs, dense_seen = None, set()
     MASK = (1 << 40) - 1
     ahead = getattr(ctx, "plans", None) or {}
-    for grp in _sparse_group_cache(plan, tables):
+    for grp in _sparse_group_cache(plan, tables, getattr(ctx, "rows_key", None)):
         D, fs, tabs, n = grp["dim"], grp["fs"], grp["tabs"], grp["n"]
         dev = tables[tabs[0]].device
         pre = ahead.get((D, fs[0]))
@@ -1360,7 +1375,7 @@ class _FastForward:
         self.view["table"] = [ptrs[k] if k >= 0 else 0 for k in self.table_of]
         self.view["rows"] = [rows[k] if k >= 0 else 0 for k in self.table_of]
         self._tables_id = tables
-        self._tkey = (len(tables), ptrs[0], ptrs[-1]) if tables else None
+        self._tkey = ptrs
         self.device = tables[0].device if tables else None
 
     def __call__(self, tables, inputs, weights, out_ld, need_out, mode):
@@ -1391,7 +1406,12 @@ class _FastForward:
                             st, _, nm = _pending_status.pop(0)
                             _raise_if_oob(st, nm)
                 return res[1], res[2], res[3]
-        if tables is not self._tables_id or (tables and self._tkey != (len(tables), tables[0].data_ptr(), tables[-1].data_ptr())):
+        # a new list object is bound afresh (its tensors may be temporaries whose addresses the allocator hands out again, with other row counts:
+        # the bound list is held, so identity is reliable); the SAME list is compared by every table's address as one list -- its two ends say
+        # nothing about a table in the middle that was replaced, grown or converted (the new tensor exists before the old one goes, so its
+        # address differs).  BoundPlan::tables_unchanged also compares row counts and types; here each further probe per table costs more
+        # than the whole check (profiles/host_paths.txt)
+        if tables is not self._tables_id or self._tkey != list(map(_DATA_PTR, tables)):
             self._bind_tables(tables)
         if self.simple:
             x0 = inputs[0]
@@ -1431,8 +1451,7 @@ class _FastForward:
         else:
             status = torch.zeros(4, dtype=torch.int32, device=dev) if mode != "off" else None
         if B > 0:
-            rc = self.fwd(self.arr, self.n, B, _ptr(out), ld, _ptr(wide), plan.wide_width, _ptr(fm), None, 0, _ptr(status),
-                          torch.cuda.current_stream(dev).cuda_stream)
+            rc = self.fwd(self.arr, self.n, B, _ptr(out), ld, _ptr(wide), plan.wide_width, _ptr(fm), None, 0, _ptr(status), _raw_stream(dev))
             if rc:
                 check(rc, "nrx_embed_fwd")
         if status is not None and mode != "deferred":

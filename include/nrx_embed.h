@@ -947,6 +947,29 @@ NRX_API int nrx_rep_compact(const float* full, int32_t world, int64_t cf, int64_
                     const int64_t* rows, const int32_t* key_table, int32_t n_tables, int32_t dim, int64_t* keys, float* values,
                     int64_t cap, int64_t* n_out, void* workspace, void* stream);
 
+/* ---- in-batch softmax loss of the two-tower recall model (DSSM `negatives: in_batch`) ---------------------------------------------------
+ * u, v: fp32 [batch, dim] tower outputs (row strides u_ld, v_ld >= dim; every row 16-byte aligned), inv_t = 1 / temperature, item_ids: null or
+ * the positives' item ids [batch] (int32 / int64 by index_bits; compared at full width).
+ *   s_ij = dot(u_i, v_j) * inv_t            (the fp32 fma chain of the matrix cores over the element order j, H + j as in nrx_topk_ip, then * inv_t)
+ *   column j is EXCLUDED for row i when item_ids != null, j != i and item_ids[j] == item_ids[i]; the diagonal never is
+ *   row_lse[i] = log sum over kept j of exp(s_ij)   (running maximum: finite for any finite input)
+ *   row_loss[i] = row_lse[i] - s_ii                 (weighting and the mean stay with the caller)
+ * backward, given g_row [batch] (any sign, zeros):  p_ij = exp(s_ij - row_lse[i]) for kept j, else 0,
+ *   g_u[i, :] = g_row[i] inv_t sum_j (p_ij - [i==j]) v[j, :]        g_v[j, :] = inv_t sum_i g_row[i] (p_ij - [i==j]) u[i, :]
+ *   (g_u or g_v may be null: that side is skipped).  Two launches of one kernel with the roles swapped; the scores are recomputed.
+ * No [batch, batch] buffer: the workspace (nrx_inbatch_softmax_workspace device bytes, the same col_splits) holds batch * splits * max(3, dim)
+ * floats.  col_splits: the column range is cut into that many parts over blocks (occupancy at small batch) and the parts are merged in a fixed
+ * order; 0 = chosen from batch alone (at most 16, 1 from batch 65536 on), at most 64.  No atomics: the same bits run to run for one (batch, dim, col_splits).
+ * dim: a multiple of 4 in 4..64 (65..128: NRX_ERR_UNSUPPORTED; anything else NRX_ERR_BAD_ARG).  batch == 0: NRX_OK, nothing launched.
+ * No reference counterpart: the reference contrasts each user with 1-4 sampled items (src/model/recall/DSSM/model.py:65-99). */
+NRX_API int64_t nrx_inbatch_softmax_workspace(int64_t batch, int32_t dim, int32_t col_splits);
+NRX_API int nrx_inbatch_softmax_fwd(const float* u, int64_t u_ld, const float* v, int64_t v_ld, int64_t batch, int32_t dim, float inv_temperature,
+                            const void* item_ids, int32_t index_bits, int32_t col_splits /* 0 = choose */, float* row_loss, float* row_lse,
+                            void* workspace, void* stream);
+NRX_API int nrx_inbatch_softmax_bwd(const float* u, int64_t u_ld, const float* v, int64_t v_ld, int64_t batch, int32_t dim, float inv_temperature,
+                            const void* item_ids, int32_t index_bits, int32_t col_splits, const float* row_lse, const float* g_row,
+                            float* g_u, int64_t gu_ld, float* g_v, int64_t gv_ld, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

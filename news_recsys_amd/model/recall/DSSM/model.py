@@ -43,6 +43,12 @@ class DSSM(BaseModel):
         self.val_dataloader_ = dataloaders.get("val_dataloader", None)
         self.user_id_feature = self.hparams_.get("user_id_feature", "user_id")
         self.item_id_feature = self.hparams_.get("item_id_feature", "movie_id")
+        # training objective: "sampled" = the reference's negative_sample_rate random permutations of the batch (model.py:65-99);
+        # "in_batch" = softmax over every other item of the batch in one fused op (ops.inbatch_softmax), no [B, B] matrix
+        self.negatives = self.hparams_.get("negatives", "sampled")
+        if self.negatives not in ("sampled", "in_batch"):
+            raise ValueError(f"hparams['negatives'] must be 'sampled' or 'in_batch', got {self.negatives!r}")
+        self.in_batch_mask_same_item = bool(self.hparams_.get("in_batch_mask_same_item", True))
         if not hasattr(self, "user_history"):      # BaseModel.__init__ has loaded paths.user_history_path if configured
             self.user_history = {}
         self.emb_idx_2_val_dict = None        # optional {feature: {str(emb idx): true id}} (reference model.py:205,215)
@@ -65,6 +71,8 @@ class DSSM(BaseModel):
     def forward(self, x, perms=None):
         user_emb = self.user_fc(self.get_user_embedding(x))
         item_emb = self.item_fc(self.get_item_embedding(x))
+        if self.negatives == "in_batch":          # every other item of the batch is a negative: nothing to draw or to gather
+            return (F.normalize(user_emb, p=2, dim=1), F.normalize(item_emb, p=2, dim=1), None)
         B = item_emb.size(0)
         n_neg = int(self.hparams_.get("negative_sample_rate", 1))
         neg = []
@@ -98,7 +106,28 @@ class DSSM(BaseModel):
             losses = losses * mask
         return losses.mean()
 
+    def in_batch_softmax_loss(self, user_emb, item_emb, temperature=0.1, mask=None, item_ids=None):
+        """Softmax cross-entropy of every user against ALL items of the batch (the infoNCE loss above with the B - 1 other items as
+        negatives); with `item_ids` [B], a column that holds the row's own item is left out of the row's softmax.  Weighting and the
+        mean are infoNCE_loss's: (row losses * mask).mean()."""
+        losses = ops.inbatch_softmax(user_emb, item_emb, temperature=temperature, item_ids=item_ids)
+        if mask is not None:
+            losses = losses * mask
+        return losses.mean()
+
     def training_step(self, batch, batch_idx):
+        if self.negatives == "in_batch":
+            item_ids = None
+            if self.in_batch_mask_same_item:
+                if self.item_id_feature not in batch:
+                    raise KeyError(f"in_batch_mask_same_item needs the batch column '{self.item_id_feature}' (hparams['item_id_feature']); "
+                                   "set hparams['in_batch_mask_same_item'] = False to train without the same-item mask")
+                item_ids = batch[self.item_id_feature].reshape(-1)
+            user_emb, item_emb, _ = self.forward(batch)
+            loss = self.in_batch_softmax_loss(user_emb, item_emb, temperature=self.hparams_.get("temperature", 0.1),
+                                              mask=batch["label"][:, 1], item_ids=item_ids)
+            self.log("train_loss", loss)
+            return loss
         user_emb, item_emb, neg_item_emb = self.forward(batch)
         loss = self.infoNCE_loss(user_emb, item_emb, neg_item_emb, mask=batch["label"][:, 1])
         self.log("train_loss", loss)

@@ -2758,6 +2758,81 @@ def topk_ip(items: torch.Tensor, queries: torch.Tensor, k: int, exclude=None):
     return torch.cat(idxs, dim=1), torch.cat(scs, dim=1)
 
 
+def _rows16(t: torch.Tensor, what: str) -> torch.Tensor:
+    """[B, d] fp32 on the device whose rows the kernels can read as float4s in place (unit column stride, row stride % 4 == 0, 16-byte
+    aligned base: a column slice of a wider buffer qualifies), else a contiguous copy."""
+    _dev(t, what)
+    if t.dtype != torch.float32:
+        raise TypeError(f"{what}: expected float32, got {t.dtype}")
+    if t.dim() != 2:
+        raise ValueError(f"{what}: expected [batch, dim], got {tuple(t.shape)}")
+    if t.shape[0] > 1 and (t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.stride(0) % 4 != 0 or t.data_ptr() % 16 != 0):
+        return t.contiguous()
+    if t.shape[0] <= 1 and (not t.is_contiguous() or t.data_ptr() % 16 != 0):
+        return t.contiguous()
+    return t
+
+
+class _InbatchSoftmaxFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, v, ids, inv_t, col_splits):
+        lib = _lib.load()
+        B, d = u.shape
+        dev = u.device
+        row_loss = torch.empty(B, dtype=torch.float32, device=dev)
+        row_lse = torch.empty(B, dtype=torch.float32, device=dev)
+        nbytes = lib.nrx_inbatch_softmax_workspace(B, d, col_splits)
+        ws = torch.empty(max(nbytes, 0), dtype=torch.uint8, device=dev)      # (a refused size: the call below refuses the same arguments, with its own code and message)
+        bits = 64 if ids is not None and ids.dtype == torch.int64 else 32
+        check(lib.nrx_inbatch_softmax_fwd(u.data_ptr(), u.stride(0) if B > 1 else d, v.data_ptr(), v.stride(0) if B > 1 else d, B, d, inv_t,
+                                          _ptr(ids), bits, col_splits, row_loss.data_ptr(), row_lse.data_ptr(), ws.data_ptr(),
+                                          _stream_ptr(u)), "nrx_inbatch_softmax_fwd")
+        ctx.save_for_backward(u, v, row_lse, ids)
+        ctx.cfg = (inv_t, col_splits, bits, nbytes)
+        ctx.mark_non_differentiable(row_lse)
+        return row_loss, row_lse
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_lse):
+        lib = _lib.load()
+        u, v, row_lse, ids = ctx.saved_tensors
+        inv_t, col_splits, bits, nbytes = ctx.cfg
+        B, d = u.shape
+        need_u, need_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        g = g_loss if g_loss.is_contiguous() and g_loss.dtype == torch.float32 else g_loss.contiguous().float()
+        g_u = torch.empty((B, d), dtype=torch.float32, device=u.device) if need_u else None
+        g_v = torch.empty((B, d), dtype=torch.float32, device=u.device) if need_v else None
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=u.device)
+        check(lib.nrx_inbatch_softmax_bwd(u.data_ptr(), u.stride(0) if B > 1 else d, v.data_ptr(), v.stride(0) if B > 1 else d, B, d, inv_t,
+                                          _ptr(ids), bits, col_splits, row_lse.data_ptr(), g.data_ptr(), _ptr(g_u), d, _ptr(g_v), d,
+                                          ws.data_ptr(), _stream_ptr(u)), "nrx_inbatch_softmax_bwd")
+        return g_u, g_v, None, None, None
+
+
+def inbatch_softmax(u: torch.Tensor, v: torch.Tensor, temperature: float = 0.1, item_ids: Optional[torch.Tensor] = None,
+                    col_splits: int = 0) -> torch.Tensor:
+    """In-batch softmax loss rows of a two-tower model: row_loss[i] = log sum_j exp(u_i . v_j / temperature) - u_i . v_i / temperature over
+    every item j of the batch, minus the columns j != i that hold row i's own item (item_ids [B] int32 / int64, optional).  u, v [B, d] fp32
+    on the GPU, d a multiple of 4 up to 64.  The [B, B] matrix is never formed (nrx_inbatch_softmax_fwd / _bwd: the scores live in matrix-core
+    accumulators and are recomputed in the backward); differentiable in u and v; no host synchronisation, so it can be graph-captured.
+    col_splits: 0 = let the library choose how many blocks share a row's columns; any fixed value gives the same bits run to run."""
+    u = _rows16(u, "inbatch_softmax: u")
+    v = _rows16(v, "inbatch_softmax: v")
+    if u.shape != v.shape:
+        raise ValueError(f"inbatch_softmax: u {tuple(u.shape)} vs v {tuple(v.shape)}")
+    if not (temperature > 0.0):
+        raise ValueError("inbatch_softmax: temperature must be positive")
+    ids = None
+    if item_ids is not None:
+        ids = _dev(item_ids, "inbatch_softmax: item_ids").reshape(-1)
+        if ids.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"inbatch_softmax: item_ids must be int32 or int64, got {ids.dtype}")
+        if ids.numel() != u.shape[0]:
+            raise ValueError(f"inbatch_softmax: {ids.numel()} item ids for a batch of {u.shape[0]}")
+        ids = ids.contiguous()
+    return _InbatchSoftmaxFn.apply(u, v, ids, 1.0 / float(temperature), int(col_splits))[0]
+
+
 def device_info(device: int = 0):
     lib = _lib.load()
     info = (C.c_int64 * 6)()

@@ -1,5 +1,7 @@
-"""Opt-in MLP weight gradient (nrx_linear_wgrad, ops.linear): gradients against torch's own nn.Linear in fp64, and the
-drop-in property of the layer class (same parameters and state_dict keys as the reference's MLP, src/model/model_utils/utils.py:6-17)."""
+"""Opt-in MLP weight gradient (ops.linear): gradients against torch's own nn.Linear in fp64, and the drop-in property of the layer class.  With the
+default NRX_WGRAD=auto every shape here takes nrx_linear_wgrad_ordered (their scratch is far below ops.LINEAR_ORDERED_MAX); the atomic entry
+nrx_linear_wgrad and both entries' launch-shape edges are run by tests/test_wgrad_exact_gpu.py.  The layer class has the
+same parameters and state_dict keys as the reference's MLP (src/model/model_utils/utils.py:6-17)."""
 import pytest
 import torch
 
@@ -21,6 +23,8 @@ def test_mlp_state_dict_keys_same_with_and_without_switch(monkeypatch):
 @pytest.mark.parametrize("batch,in_f,out_f", [(1, 4, 4), (257, 416, 128), (4096, 128, 64), (1000, 64, 1), (777, 37, 19), (65536, 128, 128),
                                                (3, 1, 1), (5000, 1000, 130)])
 def test_linear_grads_match_fp64(batch, in_f, out_f):
+    """ops.linear in its default mode against fp64.  All eight shapes take nrx_linear_wgrad_ordered (NRX_WGRAD=auto: the ordered entry while its scratch
+    is at most ops.LINEAR_ORDERED_MAX = 64 MiB; the largest here, (65536, 128, 128), needs 8.45 MB), not the atomic nrx_linear_wgrad."""
     from news_recsys_amd import ops
     g = torch.Generator(device="cuda").manual_seed(batch + in_f)
     a = torch.randn(batch, in_f, device="cuda", generator=g, requires_grad=True)

@@ -904,7 +904,11 @@ NRX_API int nrx_csr_to_padded(const void* values, int32_t value_bits, const int6
  * user's samples are contiguous, seg_start[u] .. seg_start[u+1), and inside a segment they are in the
  * order of Python's stable sorted(items, key=score, reverse=True).  scores fp32, labels fp32 (1 = positive).
  * Outputs, fp64 [n_users] each: auc (NaN when the user has a single class -- the reference skips those),
- * ndcg@k, hr@k, mrr@k (0 for users without positives, as the reference records them).            */
+ * ndcg@k, hr@k, mrr@k (0 for users without positives, as the reference records them).
+ * Non-finite scores (the per-user body and its rules: csrc/nrx_rank_metrics.h; it terminates on any input): a user with ANY NaN or +-inf score
+ * gets auc = NaN -- sklearn's roc_auc_score raises for such a score and the reference's try/except then skips the user, as it skips a single-class
+ * one; ndcg / hr / mrr are taken from the order the caller supplied (scores are not compared for them) and are always finite and in [0, 1].
+ * An empty segment (seg_start[u] == seg_start[u+1]) gives auc = NaN and ndcg = hr = mrr = 0.  n_users == 0 returns NRX_OK and reads no pointer. */
 NRX_API int nrx_user_rank_metrics(const float* scores, const float* labels, const int64_t* seg_start, int64_t n_users,
                           int32_t k, double* auc, double* ndcg, double* hr, double* mrr, void* stream);
 /* Exact inner-product top-k retrieval (replaces faiss.IndexFlatIP.search as wrapped by

@@ -6,11 +6,16 @@ per-user sklearn AUC / NDCG@10 / HR@10 / MRR@10, a warm/cold split by `train_use
 AUC / LogLoss in Python at epoch end (:333-492), then prints / appends a fixed-format block to
 `val_log.log` (:494-528, parsed by scripts/log_analysis.py:16-23).
 
-Here the epoch's samples stay on the GPU: two stable sorts order them by (user, score desc, arrival),
+Here the epoch's samples stay on the GPU: two stable sorts order them by (user, score desc, arrival; torch's
+descending stable sort puts NaN first and keeps arrival order among equal scores),
 ONE kernel (`nrx_user_rank_metrics`, one thread per user segment) yields the per-user metrics in fp64,
 and the global AUC (ties at 1/2, like sklearn) / LogLoss are a handful of fp64 tensor reductions.
 `ranking_metrics` returns the same nested dict as the reference's `results`; `format_val_log` renders
-the same text."""
+the same text.
+
+Non-finite scores (a diverged model): a user with a NaN / +-inf score has per-user AUC NaN and drops out of GAUC like a
+single-class user, the global AUC of a group that holds one is 0.0, LogLoss keeps its float32 formula (NaN in, NaN out);
+NDCG / HR / MRR follow the sorted order and stay finite (csrc/nrx_rank_metrics.h)."""
 from __future__ import annotations
 
 from typing import Dict, Iterable, Optional
@@ -22,11 +27,12 @@ from .ops import _dev, _stream_ptr
 
 
 def _auc_ties(scores: torch.Tensor, labels: torch.Tensor) -> float:
-    """Global AUC with ties counted 1/2 (what sklearn.roc_auc_score returns); 0.0 when one class only."""
+    """Global AUC with ties counted 1/2 (what sklearn.roc_auc_score returns); 0.0 when one class only, and 0.0 for a group that holds a NaN or
+    +-inf score: roc_auc_score raises for one and the reference's bare `except` leaves the AUC at 0.0 (base_model.py:446-450)."""
     y = (labels == 1).to(torch.float64)
     P = y.sum()
     N = y.numel() - P
-    if y.numel() == 0 or P.item() == 0 or N.item() == 0:
+    if y.numel() == 0 or P.item() == 0 or N.item() == 0 or not bool(torch.isfinite(scores).all()):
         return 0.0
     s, order = torch.sort(scores, descending=True, stable=True)
     y = y[order]

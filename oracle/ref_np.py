@@ -703,15 +703,19 @@ def pool_inbox(tables, feat_table, batch: int, world: int, cap: int, recv2d, inb
 # validation metrics                               src/model/BaseModel/base_model.py:320-528
 # ----------------------------------------------------------------------------------------
 def auc_ties(scores: np.ndarray, labels: np.ndarray) -> float:
-    """roc_auc_score for binary labels (what sklearn computes: trapezoid = Mann-Whitney with ties at 0.5)."""
+    """roc_auc_score for binary labels (what sklearn computes: trapezoid = Mann-Whitney with ties at 0.5).
+    NaN for a NaN or +-inf score: sklearn raises ValueError there (the callers below do what the reference's try/except does with it).
+    Every pass of the tie loop consumes entry i itself, so it ends on any input."""
     s = np.asarray(scores, np.float64)
     y = np.asarray(labels, np.float64)
+    if not np.isfinite(s).all():
+        return float("nan")
     P, N = float((y == 1).sum()), float((y != 1).sum())
     order = np.argsort(-s, kind="stable")
     s, y = s[order], y[order]
     num, neg_above, i = 0.0, 0.0, 0
     while i < s.size:
-        j = i
+        j = i + 1
         while j < s.size and s[j] == s[i]:
             j += 1
         p = float((y[i:j] == 1).sum())
@@ -722,9 +726,42 @@ def auc_ties(scores: np.ndarray, labels: np.ndarray) -> float:
     return num / (P * N)
 
 
+def rank_key(score: float):
+    """Sort key (use with reverse=True) of the per-user ranking.  For numbers it is the reference's sorted(items, key=score, reverse=True)
+    (base_model.py:381): stable, ties keep arrival order.  With a NaN the reference's sorted() is undefined (every comparison is false, the result
+    depends on the arrival pattern); this oracle ADOPTS: NaN ranks above every number (+inf included), arrival order among NaN -- what torch's
+    descending stable sort does."""
+    return (True, 0.0) if score != score else (False, score)
+
+
+def user_rank_metrics(scores, labels, k: int = 10):
+    """One user's (auc, ndcg@k, hr@k, mrr@k) from the samples ALREADY in ranked order (rank_key) -- the definition of nrx_user_rank_metrics for
+    one segment, base_model.py:376-433.  label == 1 is a positive.
+      auc   ties at 1/2; NaN when the user has one class only (the reference skips the user, :378), when the segment is empty, and when any
+            score is NaN or +-inf (roc_auc_score raises, the reference's try/except skips the user the same way, :380-386);
+      ndcg / hr / mrr   from the first k entries in the order given, scores never compared: finite and in [0, 1]; 0 without a positive."""
+    s = [float(x) for x in scores]
+    y = [float(x) for x in labels]
+    npos = sum(1 for v in y if v == 1)
+    nneg = len(y) - npos
+    auc = float("nan")
+    if npos and nneg and all(math.isfinite(v) for v in s):
+        auc = auc_ties(np.array(s), np.array(y))          # (already descending: the stable argsort inside keeps the order)
+    if npos == 0:
+        return auc, 0.0, 0.0, 0.0
+    top = y[:k]
+    hr = 1.0 if any(v == 1 for v in top) else 0.0
+    dcg = sum(1.0 / np.log2(r + 1) for r, v in enumerate(top, start=1) if v == 1)
+    idcg = sum(1.0 / np.log2(r + 1) for r in range(1, min(npos, k) + 1))
+    mrr = next((1.0 / r for r, v in enumerate(top, start=1) if v == 1), 0.0)
+    return auc, (float(dcg / idcg) if idcg > 0 else 0.0), hr, mrr
+
+
 def validation_metrics(user_ids, scores, labels, warm_users, k: int = 10):
     """Restatement of BaseModel.on_validation_epoch_end (base_model.py:333-492) over flat arrays in the
-    order validation_step appended them (:320-330).  Returns the same nested dict as its `results`."""
+    order validation_step appended them (:320-330).  Returns the same nested dict as its `results`.
+    Non-finite scores: a user that holds a NaN / +-inf score contributes no AUC to GAUC, the global AUC of a group that holds one is 0.0 (the
+    reference's two try/except around roc_auc_score); the ranking follows rank_key; LogLoss is the float32 formula as written (NaN in, NaN out)."""
     groups = {}
     for u, s, y in zip(user_ids, scores, labels):
         groups.setdefault(int(u), []).append((float(s), float(y)))
@@ -738,30 +775,23 @@ def validation_metrics(user_ids, scores, labels, warm_users, k: int = 10):
         for dst in (lists["Overall"], tgt):
             dst["p"].extend(preds)
             dst["y"].extend(labs)
-        if len(set(labs)) > 1:
-            a = auc_ties(np.array(preds), np.array(labs))
+        ranked = sorted(items, key=lambda x: rank_key(x[0]), reverse=True)      # stable: ties keep arrival order
+        a, ndcg, hr, mrr = user_rank_metrics([x[0] for x in ranked], [x[1] for x in ranked], k)
+        if len(set(labs)) > 1 and not math.isnan(a):
             lists["Overall"]["auc"].append(a)
             tgt["auc"].append(a)
-        top = sorted(items, key=lambda x: x[0], reverse=True)[:k]      # stable: ties keep arrival order
-        npos = sum(1 for x in items if x[1] == 1)
-        if npos == 0:
-            vals = (0.0, 0.0, 0.0)
-        else:
-            hr = 1.0 if any(x[1] == 1 for x in top) else 0.0
-            dcg = sum(1.0 / np.log2(r + 1) for r, (_, y) in enumerate(top, start=1) if y == 1)
-            idcg = sum(1.0 / np.log2(r + 1) for r in range(1, min(npos, k) + 1))
-            mrr = next((1.0 / r for r, (_, y) in enumerate(top, start=1) if y == 1), 0.0)
-            vals = (hr, dcg / idcg if idcg > 0 else 0.0, mrr)
         for dst in (lists["Overall"], tgt):
-            dst["hr"].append(vals[0])
-            dst["ndcg"].append(vals[1])
-            dst["mrr"].append(vals[2])
+            dst["hr"].append(hr)
+            dst["ndcg"].append(ndcg)
+            dst["mrr"].append(mrr)
 
     def auc_logloss(p, y):
         if not p:
             return 0.0, 0.0
         p, y = np.array(p, np.float32), np.array(y, np.float32)
         auc = auc_ties(p, y) if len(set(y.tolist())) > 1 else 0.0
+        if math.isnan(auc):          # a non-finite score: roc_auc_score raised, the bare except leaves 0.0 (:446-450)
+            auc = 0.0
         # As written in the reference (:445-449): the scores are float32, so the clip's upper bound
         # 1 - 1e-15 rounds to exactly 1.0 and a score of 1.0 gives log(0): LogLoss = inf / nan.
         with np.errstate(divide="ignore", invalid="ignore"):

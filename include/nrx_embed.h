@@ -974,6 +974,36 @@ NRX_API int nrx_inbatch_softmax_bwd(const float* u, int64_t u_ld, const float* v
                             const void* item_ids, int32_t index_bits, int32_t col_splits, const float* row_lse, const float* g_row,
                             float* g_u, int64_t gu_ld, float* g_v, int64_t gv_ld, void* workspace, void* stream);
 
+/* ---- candidate softmax: the loss above over a RECTANGULAR candidate set with a per-column additive term (mixed negative sampling and the
+ * logQ correction of DSSM `negatives: in_batch`).  The same kernel template: the in-batch entry points are this path with
+ * n_cand == batch and no bias, bit for bit.
+ * u: fp32 [batch, dim]; v: fp32 [n_cand, dim] with n_cand >= batch: row i < batch is row i's positive, rows batch..n_cand-1 are extra
+ * negatives; cand_ids: null or [n_cand] (int32 / int64 by index_bits); col_bias: null or fp32 [n_cand], finite, never read on the host and
+ * not differentiated.
+ *   z_ij = dot(u_i, v_j) * inv_t + col_bias[j]     (the score s_ij as above, then ONE more rounded addition; never contracted into an fma)
+ *   column j is EXCLUDED for row i when cand_ids != null, j != i and cand_ids[j] == cand_ids[i] -- extras included: a sampled item that
+ *   happens to be the row's own item is not a negative; the diagonal never is
+ *   row_lse[i] = log sum over kept j < n_cand of exp(z_ij)        row_loss[i] = row_lse[i] - z_ii
+ * backward, given g_row [batch]:  p_ij = exp(z_ij - row_lse[i]) for kept j, else 0,
+ *   g_u[i, :] = g_row[i] inv_t sum_{j < n_cand} (p_ij - [i==j]) v[j, :]          (g_u: [batch, gu_ld])
+ *   g_v[j, :] = inv_t sum_{i < batch} g_row[i] (p_ij - [i==j]) u[i, :]           (g_v: [n_cand, gv_ld], every row written)
+ * z_ij is one value in the forward and both gradient roles: a row whose only kept column is its diagonal has loss 0.0 and zero gradients
+ * exactly, whatever finite bias it carries; a bias of zeros gives the bits of no bias.
+ * Forward and g_u keep the users in registers and stream the n_cand candidates; g_v keeps the candidates and streams the users.  col_splits
+ * cuts the STREAMED side of each launch; 0 = chosen per launch from its (owned, streamed) row counts (n_cand == batch: the in-batch choice).
+ * No atomics: the same bits run to run for one (batch, n_cand, dim, col_splits).  Workspace (nrx_cand_softmax_workspace bytes, the same
+ * col_splits): max(batch (2 splits + 1), splits * owned * dim of a split backward role) floats -- never batch * n_cand.
+ * n_cand < batch or n_cand >= 2^31 - 128: NRX_ERR_BAD_ARG; dim, strides, alignment and null buffers as above (col_bias 4-byte aligned).
+ * batch == 0: NRX_OK, nothing launched and NOTHING WRITTEN -- g_v's n_cand rows are zero by definition and left to the caller. */
+NRX_API int64_t nrx_cand_softmax_workspace(int64_t batch, int64_t n_cand, int32_t dim, int32_t col_splits);
+NRX_API int nrx_cand_softmax_fwd(const float* u, int64_t u_ld, const float* v, int64_t v_ld, int64_t batch, int64_t n_cand, int32_t dim,
+                         float inv_temperature, const void* cand_ids, int32_t index_bits, const float* col_bias /* or null */,
+                         int32_t col_splits /* 0 = choose */, float* row_loss, float* row_lse, void* workspace, void* stream);
+NRX_API int nrx_cand_softmax_bwd(const float* u, int64_t u_ld, const float* v, int64_t v_ld, int64_t batch, int64_t n_cand, int32_t dim,
+                         float inv_temperature, const void* cand_ids, int32_t index_bits, const float* col_bias, int32_t col_splits,
+                         const float* row_lse, const float* g_row, float* g_u, int64_t gu_ld, float* g_v, int64_t gv_ld, void* workspace,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,8 @@ fused HIP launch per tower; towers / normalize / losses are plain torch.
 Deviations, all documented in SURVEY: features are concatenated in SORTED order (the reference iterates
 a Python set: order depends on PYTHONHASHSEED); `forward(x, perms=None)` accepts explicit negative-
 sampling permutations so results are reproducible (the reference draws torch.randperm, :63).
+`negatives: in_batch` (no reference counterpart) trains against every other item of the batch, optionally plus `extra_negatives` items
+drawn uniformly from the corpus and with the logQ correction of the logits (`forward(x, perms=None, extra_idx=None)`).
 
 Recall evaluation (`on_train_epoch_end` :230-254, `hit_rate` :182-228): the reference builds a faiss
 IndexFlatIP on the host and searches one user at a time (it raises unless batch_size == 1), over-fetching
@@ -49,6 +51,20 @@ class DSSM(BaseModel):
         if self.negatives not in ("sampled", "in_batch"):
             raise ValueError(f"hparams['negatives'] must be 'sampled' or 'in_batch', got {self.negatives!r}")
         self.in_batch_mask_same_item = bool(self.hparams_.get("in_batch_mask_same_item", True))
+        # in_batch only.  extra_negatives = E: mixed negative sampling (Yang et al. 2020) -- E items drawn uniformly from the corpus
+        # (set_negative_corpus) join the batch's items as negatives of every row.  logq_correction: column j's logit gets
+        # -log(B p[id_j] + E / M), the expected number of times item j appears among the candidates (Yi et al. 2019; set_item_counts gives p)
+        E = self.hparams_.get("extra_negatives", 0)
+        if isinstance(E, bool) or not isinstance(E, int) or E < 0:
+            raise ValueError(f"hparams['extra_negatives'] must be an integer >= 0, got {E!r}")
+        self.extra_negatives = E
+        self.logq_correction = self.hparams_.get("logq_correction", False)
+        if not isinstance(self.logq_correction, bool):
+            raise ValueError(f"hparams['logq_correction'] must be a bool, got {self.logq_correction!r}")
+        if self.negatives != "in_batch" and (self.extra_negatives > 0 or self.logq_correction):
+            raise ValueError("hparams['extra_negatives'] and hparams['logq_correction'] belong to negatives: 'in_batch'")
+        self.negative_corpus = None           # {column: [M, ...] device tensor} of every corpus item (set_negative_corpus)
+        self.register_buffer("item_probs", None, persistent=False)      # p[item id] (set_item_counts); not part of the state_dict
         if not hasattr(self, "user_history"):      # BaseModel.__init__ has loaded paths.user_history_path if configured
             self.user_history = {}
         self.emb_idx_2_val_dict = None        # optional {feature: {str(emb idx): true id}} (reference model.py:205,215)
@@ -68,11 +84,76 @@ class DSSM(BaseModel):
     def get_features_embedding(self, feature_name, feature_value):
         return self.get_feature_embedding(feature_name, feature_value)
 
-    def forward(self, x, perms=None):
+    # ---- mixed negative sampling and the logQ correction (negatives: in_batch) ----------------------------
+    def set_negative_corpus(self, columns=None):
+        """Keep the item tower's input columns and the item id column of all M corpus items on the device: {name: [M, ...]}.  Without
+        arguments they are read from `movies_dataloader` (the loader build_item_index walks).  extra_negatives draws from them."""
+        names = sorted(self.item_feature_names) + [self.item_id_feature]
+        if columns is None:
+            if self.movies_dataloader is None:
+                raise ValueError("set_negative_corpus() needs columns or dataloaders['movies_dataloader']")
+            parts = {}
+            for batch in self.movies_dataloader:
+                for k, v in batch.items():
+                    if isinstance(v, torch.Tensor) and (k in names or (k.endswith("_mask") and k[:-len("_mask")] in names)):
+                        parts.setdefault(k, []).append(v)
+            columns = {k: torch.cat(v, dim=0) for k, v in parts.items()}
+        if self.item_id_feature not in columns:
+            raise KeyError(f"the negative corpus needs the item id column '{self.item_id_feature}' (hparams['item_id_feature'])")
+        if any(k.endswith("_offsets") for k in columns):
+            raise ValueError("the negative corpus is gathered row by row: array features must be padded [M, L] columns with a _mask, not CSR offsets")
+        M = columns[self.item_id_feature].reshape(-1).shape[0]
+        if M == 0 or any(not isinstance(v, torch.Tensor) or v.dim() == 0 or v.shape[0] != M for v in columns.values()):
+            raise ValueError(f"every column of the negative corpus must be a tensor with one row per item ({M} item ids)")
+        self.negative_corpus = {k: v.to(self.device) for k, v in columns.items()}
+        return self.negative_corpus
+
+    def set_item_counts(self, counts, smoothing=1.0):
+        """Item frequencies for the logQ correction: p = (counts + smoothing) / (sum(counts) + smoothing * len(counts)), indexed by item
+        id.  A non-persistent buffer: it follows .to(device) and stays out of the state_dict."""
+        c = torch.as_tensor(counts).reshape(-1).to(torch.float64)
+        if c.numel() == 0 or not bool(torch.isfinite(c).all()) or bool((c < 0).any()) or not (smoothing >= 0.0):
+            raise ValueError("set_item_counts: counts must be a non-empty vector of finite values >= 0, smoothing >= 0")
+        total = float(c.sum()) + float(smoothing) * c.numel()
+        if not total > 0.0:
+            raise ValueError("set_item_counts: all counts are zero and smoothing is 0")
+        self.item_probs = ((c + float(smoothing)) / total).to(torch.float32).to(self.device)
+        return self.item_probs
+
+    def _draw_extra_idx(self, device):
+        if self.negative_corpus is None:
+            raise ValueError("hparams['extra_negatives'] > 0 needs the corpus to draw from: call set_negative_corpus() first")
+        M = self.negative_corpus[self.item_id_feature].shape[0]
+        return torch.randint(0, M, (self.extra_negatives,), device=device)
+
+    def _extra_columns(self, extra_idx):
+        if self.negative_corpus is None:
+            raise ValueError("hparams['extra_negatives'] > 0 needs the corpus to draw from: call set_negative_corpus() first")
+        idx = extra_idx.reshape(-1)
+        return {k: v.index_select(0, idx.to(v.device)) for k, v in self.negative_corpus.items()}
+
+    def logq_bias(self, cand_ids, batch_size):
+        """-log(B p[id_j] + E / M) per candidate column: the log of the expected number of appearances of item j among the B in-batch
+        items (drawn by popularity) and the E uniform extras (E / M; 0 when E == 0).  The positives' columns are corrected too."""
+        if self.item_probs is None:
+            raise ValueError("hparams['logq_correction'] needs the item frequencies: call set_item_counts() first")
+        q = float(batch_size) * self.item_probs[cand_ids.reshape(-1).to(torch.int64)]
+        if self.extra_negatives > 0:
+            if self.negative_corpus is None:
+                raise ValueError("hparams['extra_negatives'] > 0 needs the corpus to draw from: call set_negative_corpus() first")
+            q = q + float(self.extra_negatives) / float(self.negative_corpus[self.item_id_feature].shape[0])
+        return -torch.log(q)
+
+    def forward(self, x, perms=None, extra_idx=None):
         user_emb = self.user_fc(self.get_user_embedding(x))
         item_emb = self.item_fc(self.get_item_embedding(x))
         if self.negatives == "in_batch":          # every other item of the batch is a negative: nothing to draw or to gather
-            return (F.normalize(user_emb, p=2, dim=1), F.normalize(item_emb, p=2, dim=1), None)
+            extra = None
+            if self.extra_negatives > 0:          # ... plus E corpus items through the same tower (gradients reach the tower and the tables)
+                if extra_idx is None:
+                    extra_idx = self._draw_extra_idx(item_emb.device)
+                extra = F.normalize(self.item_fc(self.get_item_embedding(self._extra_columns(extra_idx))), p=2, dim=1)
+            return (F.normalize(user_emb, p=2, dim=1), F.normalize(item_emb, p=2, dim=1), extra)
         B = item_emb.size(0)
         n_neg = int(self.hparams_.get("negative_sample_rate", 1))
         neg = []
@@ -106,26 +187,43 @@ class DSSM(BaseModel):
             losses = losses * mask
         return losses.mean()
 
-    def in_batch_softmax_loss(self, user_emb, item_emb, temperature=0.1, mask=None, item_ids=None):
+    def in_batch_softmax_loss(self, user_emb, item_emb, temperature=0.1, mask=None, item_ids=None, extra_item_emb=None, col_bias=None):
         """Softmax cross-entropy of every user against ALL items of the batch (the infoNCE loss above with the B - 1 other items as
-        negatives); with `item_ids` [B], a column that holds the row's own item is left out of the row's softmax.  Weighting and the
-        mean are infoNCE_loss's: (row losses * mask).mean()."""
-        losses = ops.inbatch_softmax(user_emb, item_emb, temperature=temperature, item_ids=item_ids)
+        negatives); with `item_ids`, a column that holds the row's own item is left out of the row's softmax.  Weighting and the
+        mean are infoNCE_loss's: (row losses * mask).mean().
+        extra_item_emb [E, 16]: further negatives of every row (mixed negative sampling); col_bias [B + E]: added to the columns' logits
+        (the logQ correction).  With either, item_ids holds B + E ids -- the batch's, then the extras' -- and the loss is
+        ops.candidate_softmax over the B + E candidates; with neither it is ops.inbatch_softmax as before."""
+        if extra_item_emb is None and col_bias is None:
+            losses = ops.inbatch_softmax(user_emb, item_emb, temperature=temperature, item_ids=item_ids)
+        else:
+            cand = item_emb if extra_item_emb is None else torch.cat([item_emb, extra_item_emb], dim=0)
+            losses = ops.candidate_softmax(user_emb, cand, temperature=temperature, ids=item_ids, col_bias=col_bias)
         if mask is not None:
             losses = losses * mask
         return losses.mean()
 
-    def training_step(self, batch, batch_idx):
+    def training_step(self, batch, batch_idx, extra_idx=None):
         if self.negatives == "in_batch":
+            E = self.extra_negatives
+            need_ids = self.in_batch_mask_same_item or self.logq_correction
             item_ids = None
-            if self.in_batch_mask_same_item:
+            if need_ids:
                 if self.item_id_feature not in batch:
                     raise KeyError(f"in_batch_mask_same_item needs the batch column '{self.item_id_feature}' (hparams['item_id_feature']); "
-                                   "set hparams['in_batch_mask_same_item'] = False to train without the same-item mask")
+                                   "set hparams['in_batch_mask_same_item'] = False to train without the same-item mask"
+                                   + (" (logq_correction needs the column too)" if self.logq_correction else ""))
                 item_ids = batch[self.item_id_feature].reshape(-1)
-            user_emb, item_emb, _ = self.forward(batch)
-            loss = self.in_batch_softmax_loss(user_emb, item_emb, temperature=self.hparams_.get("temperature", 0.1),
-                                              mask=batch["label"][:, 1], item_ids=item_ids)
+            if E > 0 and extra_idx is None:
+                extra_idx = self._draw_extra_idx(batch["label"].device)
+            user_emb, item_emb, extra_emb = self.forward(batch, extra_idx=extra_idx)
+            if E > 0 and need_ids:              # the candidates' ids: the batch's, then the extras'
+                extra_ids = self.negative_corpus[self.item_id_feature].reshape(-1).index_select(0, extra_idx.reshape(-1).to(item_ids.device))
+                item_ids = torch.cat([item_ids, extra_ids.to(item_ids.dtype)], dim=0)
+            col_bias = self.logq_bias(item_ids, user_emb.shape[0]) if self.logq_correction else None
+            loss = self.in_batch_softmax_loss(user_emb, item_emb, temperature=self.hparams_.get("temperature", 0.1), mask=batch["label"][:, 1],
+                                              item_ids=item_ids if self.in_batch_mask_same_item else None, extra_item_emb=extra_emb,
+                                              col_bias=col_bias)
             self.log("train_loss", loss)
             return loss
         user_emb, item_emb, neg_item_emb = self.forward(batch)

@@ -2833,6 +2833,83 @@ def inbatch_softmax(u: torch.Tensor, v: torch.Tensor, temperature: float = 0.1, 
     return _InbatchSoftmaxFn.apply(u, v, ids, 1.0 / float(temperature), int(col_splits))[0]
 
 
+class _CandidateSoftmaxFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, v, ids, bias, inv_t, col_splits):
+        lib = _lib.load()
+        B, d = u.shape
+        N = v.shape[0]
+        dev = u.device
+        row_loss = torch.empty(B, dtype=torch.float32, device=dev)
+        row_lse = torch.empty(B, dtype=torch.float32, device=dev)
+        nbytes = lib.nrx_cand_softmax_workspace(B, N, d, col_splits)
+        ws = torch.empty(max(nbytes, 0), dtype=torch.uint8, device=dev)      # (a refused size: the call below refuses the same arguments, with its own code and message)
+        bits = 64 if ids is not None and ids.dtype == torch.int64 else 32
+        check(lib.nrx_cand_softmax_fwd(u.data_ptr(), u.stride(0) if B > 1 else d, v.data_ptr(), v.stride(0) if N > 1 else d, B, N, d, inv_t,
+                                       _ptr(ids), bits, _ptr(bias), col_splits, row_loss.data_ptr(), row_lse.data_ptr(), ws.data_ptr(),
+                                       _stream_ptr(u)), "nrx_cand_softmax_fwd")
+        ctx.save_for_backward(u, v, row_lse, ids, bias)
+        ctx.cfg = (inv_t, col_splits, bits, nbytes)
+        ctx.mark_non_differentiable(row_lse)
+        return row_loss, row_lse
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_lse):
+        lib = _lib.load()
+        u, v, row_lse, ids, bias = ctx.saved_tensors
+        inv_t, col_splits, bits, nbytes = ctx.cfg
+        B, d = u.shape
+        N = v.shape[0]
+        need_u, need_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if B == 0:          # no row contributes: the entry point launches and writes nothing
+            return (torch.zeros_like(u) if need_u else None, torch.zeros((N, d), dtype=torch.float32, device=u.device) if need_v else None,
+                    None, None, None, None)
+        g = g_loss if g_loss.is_contiguous() and g_loss.dtype == torch.float32 else g_loss.contiguous().float()
+        g_u = torch.empty((B, d), dtype=torch.float32, device=u.device) if need_u else None
+        g_v = torch.empty((N, d), dtype=torch.float32, device=u.device) if need_v else None
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=u.device)
+        check(lib.nrx_cand_softmax_bwd(u.data_ptr(), u.stride(0) if B > 1 else d, v.data_ptr(), v.stride(0) if N > 1 else d, B, N, d, inv_t,
+                                       _ptr(ids), bits, _ptr(bias), col_splits, row_lse.data_ptr(), g.data_ptr(), _ptr(g_u), d, _ptr(g_v), d,
+                                       ws.data_ptr(), _stream_ptr(u)), "nrx_cand_softmax_bwd")
+        return g_u, g_v, None, None, None, None
+
+
+def candidate_softmax(u: torch.Tensor, v: torch.Tensor, temperature: float = 0.1, ids: Optional[torch.Tensor] = None,
+                      col_bias: Optional[torch.Tensor] = None, col_splits: int = 0) -> torch.Tensor:
+    """Softmax loss rows of a two-tower model over a candidate set larger than the batch: u [B, d], v [N, d] with N >= B, where v[i] is row
+    i's positive and v[B:] are extra negatives (mixed negative sampling);  row_loss[i] = log sum_j exp(z_ij) - z_ii  with
+    z_ij = u_i . v_j / temperature + col_bias[j] over every kept candidate j < N.  ids [N] (int32 / int64, optional): a column j != i that
+    holds row i's own item (ids[j] == ids[i]) is left out of row i's softmax, extras included.  col_bias [N] fp32 (optional): added to column
+    j's logit -- the logQ correction is col_bias[j] = -log Q_j; finite, never read on the host, not differentiated.  fp32 on the GPU, d a
+    multiple of 4 up to 64.  The [B, N] matrix is never formed (nrx_cand_softmax_fwd / _bwd: inbatch_softmax's kernels with two row
+    counts); differentiable in u and in all N rows of v; no host synchronisation, so it can be graph-captured.  With N == B and no bias the
+    result is inbatch_softmax's, bit for bit.  col_splits: as in inbatch_softmax."""
+    u = _rows16(u, "candidate_softmax: u")
+    v = _rows16(v, "candidate_softmax: v")
+    if u.shape[1] != v.shape[1]:
+        raise ValueError(f"candidate_softmax: u {tuple(u.shape)} vs v {tuple(v.shape)}")
+    if v.shape[0] < u.shape[0]:
+        raise ValueError(f"candidate_softmax: {v.shape[0]} candidates for a batch of {u.shape[0]} (v[i] is row i's positive: N >= B)")
+    if not (temperature > 0.0):
+        raise ValueError("candidate_softmax: temperature must be positive")
+    N = v.shape[0]
+    if ids is not None:
+        ids = _dev(ids, "candidate_softmax: ids").reshape(-1)
+        if ids.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"candidate_softmax: ids must be int32 or int64, got {ids.dtype}")
+        if ids.numel() != N:
+            raise ValueError(f"candidate_softmax: {ids.numel()} ids for {N} candidates")
+        ids = ids.contiguous()
+    if col_bias is not None:
+        col_bias = _dev(col_bias, "candidate_softmax: col_bias").reshape(-1)
+        if col_bias.dtype != torch.float32:
+            raise TypeError(f"candidate_softmax: col_bias must be float32, got {col_bias.dtype}")
+        if col_bias.numel() != N:
+            raise ValueError(f"candidate_softmax: {col_bias.numel()} bias values for {N} candidates")
+        col_bias = col_bias.detach().contiguous()
+    return _CandidateSoftmaxFn.apply(u, v, ids, col_bias, 1.0 / float(temperature), int(col_splits))[0]
+
+
 def device_info(device: int = 0):
     lib = _lib.load()
     info = (C.c_int64 * 6)()

@@ -1,0 +1,21 @@
+# ASan + UBSan (host side only) build of the two units the candidate softmax entry points live in (nrx_cand_softmax_workspace, _fwd, _bwd)
+# plus a driver of its own that walks their argument-validation paths (cand_softmax_validation_driver.cpp).  Run by
+# tests/test_candidate_softmax.py; no GPU needed (nothing is launched).  Same flags as inbatch.mk beside it, an object directory of its own: they may run at the same time.
+HIPCC ?= /opt/rocm/bin/hipcc
+ROOT  := $(abspath $(dir $(lastword $(MAKEFILE_LIST)))/../..)
+CSRC  := $(ROOT)/news_recsys_amd/csrc
+OUT   := $(ROOT)/tests/sanitize/_build/cand_softmax
+UNITS := nrx_lib nrx_inbatch
+# (the sanitizer flags and -fno-gpu-sanitize stay on one line: the device code is never instrumented)
+FLAGS := --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -munsafe-fp-atomics -I$(ROOT)/include -fno-omit-frame-pointer -Wno-unused-function
+FLAGS += -fsanitize=address,undefined -fno-sanitize-recover=all -fno-gpu-sanitize
+FLAGS += -Xarch_device -O0 -Xarch_device -g0
+MAKEFLAGS += -j2
+run: $(OUT)/cand_softmax_driver
+	ASAN_OPTIONS=detect_leaks=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 $(OUT)/cand_softmax_driver
+$(OUT)/%.o: $(CSRC)/%.hip $(CSRC)/nrx_common.h $(CSRC)/nrx_embed_ring.h $(ROOT)/include/nrx_embed.h
+	@mkdir -p $(OUT)
+	$(HIPCC) $(FLAGS) -c $< -o $@
+$(OUT)/cand_softmax_driver: $(UNITS:%=$(OUT)/%.o) $(ROOT)/tests/sanitize/cand_softmax_validation_driver.cpp
+	$(HIPCC) $(FLAGS) $^ -o $@
+.PHONY: run

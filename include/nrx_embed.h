@@ -525,7 +525,8 @@ NRX_API int nrx_fm_fwd(const float* feat, int64_t ld, int32_t n_fields, int32_t 
 NRX_API int nrx_fm_fwd_train(const float* feat, int64_t ld, int32_t n_fields, int32_t dim, int64_t batch,
                      float* fm_out, float* fm_sums, int64_t sums_ld, void* stream);
 /* g_feat[b, :] = (g_in ? g_in[b, :] : 0) + g_fm[b] * d fm / d feat[b, :].  g_in may be g_feat (in place) or another
- * buffer (e.g. the upstream gradient of the concat, left untouched: no copy needed) or NULL.                 */
+ * buffer (e.g. the upstream gradient of the concat, left untouched: no copy needed) or NULL.  ld, g_ld and (with g_in) g_in_ld
+ * are row strides in floats, each >= n_fields * dim (NRX_ERR_BAD_ARG otherwise, nothing enqueued).              */
 NRX_API int nrx_fm_bwd(const float* feat, int64_t ld, int32_t n_fields, int32_t dim, int64_t batch,
                const float* g_fm, const float* g_in, int64_t g_in_ld, float* g_feat, int64_t g_ld, void* stream);
 

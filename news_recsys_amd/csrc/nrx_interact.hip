@@ -911,7 +911,10 @@ extern "C" int nrx_fm_fwd_train(const float* feat, int64_t ld, int32_t n_fields,
 extern "C" int nrx_fm_bwd(const float* feat, int64_t ld, int32_t n_fields, int32_t dim, int64_t batch,
                           const float* g_fm, const float* g_in, int64_t g_in_ld, float* g_feat, int64_t g_ld, void* stream) {
     NRX_TRACE();
-    NRX_REQUIRE(feat && g_fm && g_feat && n_fields >= 1 && dim >= 1 && batch >= 0, "nrx_fm_bwd: bad argument");
+    // (the row strides as the forward checks its own: a stride below n_fields * dim makes the rows overlap -- the kernel would write over its neighbours)
+    NRX_REQUIRE(feat && g_fm && g_feat && n_fields >= 1 && dim >= 1 && batch >= 0 && ld >= (int64_t)n_fields * dim &&
+                    g_ld >= (int64_t)n_fields * dim && (g_in == nullptr || g_in_ld >= (int64_t)n_fields * dim),
+                "nrx_fm_bwd: bad argument");
     if (batch == 0) return NRX_OK;
     int ql = ceil_log2i((dim + 3) / 4);
     if (ql > 6) ql = 6;

@@ -1005,6 +1005,29 @@ NRX_API int nrx_cand_softmax_bwd(const float* u, int64_t u_ld, const float* v, i
                          const float* row_lse, const float* g_row, float* g_u, int64_t gu_ld, float* g_v, int64_t gv_ld, void* workspace,
                          void* stream);
 
+/* ---- item-based collaborative filtering (src/model/recall/ItemCF/itemCF_base.py) ---------------------------------------------
+ * nrx_itemcf_similarity: the user histories as CSR (user_off int64 [n_users + 1], items: every user's item ids STRICTLY ascending) and the
+ * transposed CSC of the same data (item_off int64 [n_items + 1], users); items / users int32 or int64 by index_bits.  With
+ *   n_i = item_off[i+1] - item_off[i],   c_ij = number of users holding both i and j (c_ii written as 0),
+ *   sim[i, j] = c_ij == 0 ? 0 : (float)((double)c_ij / sqrt((double)n_i * (double)n_j))          (fp32 [n_items, n_items], row-major)
+ * co: null, or int32 [n_items, n_items] receiving c_ij.  Items nobody holds give zero rows and columns.  One workgroup per (item, tile of
+ * col_tile columns) counts in LDS with integer adds: no global atomics, no float atomics, the same bits whatever the order of the users.
+ * col_tile: 0 = default (min(n_items, 16384)), at most 16384 and at most 65535 tiles.  workspace: none needed (may be null).
+ * nrx_itemcf_recall: for query q with history hist_items[hist_off[q] .. hist_off[q+1]) (ascending) the score of column j is
+ *   s = 0;  for i in the history, in order:  s = s + sim[i, j]                                     (plain fp32 adds)
+ * and the candidates are the columns with s > 0 that are not in the query's exclusion list (excl_off / excl_items, ascending per query; the
+ * same index_bits as hist_items).  out_idx int64 / out_score fp32 [n_queries, k]: (score desc, index asc); unused slots -1 / -FLT_MAX.
+ * k in 1..32 per call.  col_splits cuts the columns over blocks (0 = chosen, at most 1024); the result does not depend on it, bit for bit.
+ * workspace: device bytes >= nrx_itemcf_recall_workspace(n_items, n_queries, k, col_splits) (-1 for sizes the entry point refuses).
+ * Both allocate, copy and synchronise nothing (capturable); bad arguments: NRX_ERR_BAD_ARG before any launch.  n_queries == 0: NRX_OK. */
+NRX_API int nrx_itemcf_similarity(const int64_t* user_off, const void* items, int64_t n_users, const int64_t* item_off, const void* users,
+                          int64_t n_items, int32_t index_bits, int32_t col_tile /* 0 = default */, float* sim, int32_t* co /* or null */,
+                          void* workspace, void* stream);
+NRX_API int64_t nrx_itemcf_recall_workspace(int64_t n_items, int64_t n_queries, int32_t k, int32_t col_splits);
+NRX_API int nrx_itemcf_recall(const float* sim, int64_t n_items, const int64_t* hist_off, const void* hist_items, const int64_t* excl_off,
+                      const void* excl_items, int32_t index_bits, int64_t n_queries, int32_t k, int32_t col_splits /* 0 = choose */,
+                      int64_t* out_idx, float* out_score, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@ Operator                          replaces (reference file:line)
   dcn_v1 / dcn_v1_cat_             DCNLayer / DCNNet (+ torch.cat of dcn/model.py:29)  dcn/dcn_arch.py:14-30,63-70
   dcn_v2                           DCNv2Layer / DCNv2Net                dcn/dcn_arch.py:33-50,73-91
   bucketize_by_owner, gather_rows_segmented, mask_lengths   (new: row-sharded tables)
+  itemcf_similarity / itemcf_recall  compute_item_similarity / recall_top_k_items  recall/ItemCF/itemCF_base.py:18-58
 """
 from __future__ import annotations
 
@@ -2710,23 +2711,8 @@ def _topk_ip_once(items, queries, k, exclude):
     return out_idx, out_score
 
 
-def topk_ip(items: torch.Tensor, queries: torch.Tensor, k: int, exclude=None):
-    """Exact inner-product top-k (faiss.IndexFlatIP.search semantics; TopKSearcher.py:50-84).
-    items [N, d], queries [Q, d] fp32 on the GPU.  `exclude` = (offsets [Q+1], item_idx) device int64
-    CSR of per-query item positions to skip (each list ascending).  Returns (idx [Q, k] int64, score
-    [Q, k] fp32): scores descending, ties toward the lower index, empty slots -1 / -FLT_MAX.
-    k > 32 runs ceil(k / 32) passes, each excluding what the earlier ones returned (same result as one
-    pass: the order (score desc, index asc) is total)."""
-    items = _f32c(items, "items")
-    queries = _f32c(queries, "queries")
-    if items.dim() != 2 or queries.dim() != 2 or items.shape[1] != queries.shape[1]:
-        raise ValueError(f"topk_ip: items {tuple(items.shape)} vs queries {tuple(queries.shape)}")
-    if k < 1:
-        raise ValueError("topk_ip: k must be >= 1")
-    if k <= TOPK_KMAX or queries.shape[0] == 0:
-        return _topk_ip_once(items, queries, k, exclude)
-    Q = queries.shape[0]
-    dev = queries.device
+def _topk_in_passes(once, Q: int, dev, k: int, exclude):
+    """k > TOPK_KMAX: ceil(k / TOPK_KMAX) calls of once(kk, exclude) -> (idx, score), each excluding what the earlier ones returned."""
     BIG = torch.iinfo(torch.int64).max
     if exclude is not None:                                  # CSR -> padded [Q, L] with BIG as filler
         eo = exclude[0].to(device=dev, dtype=torch.int64)
@@ -2745,7 +2731,7 @@ def topk_ip(items: torch.Tensor, queries: torch.Tensor, k: int, exclude=None):
     excl = exclude
     while done < k:
         kk = min(TOPK_KMAX, k - done)
-        idx, sc = _topk_ip_once(items, queries, kk, excl)
+        idx, sc = once(kk, excl)
         idxs.append(idx)
         scs.append(sc)
         done += kk
@@ -2756,6 +2742,24 @@ def topk_ip(items: torch.Tensor, queries: torch.Tensor, k: int, exclude=None):
             torch.cumsum(valid.sum(dim=1), 0, out=offs[1:])
             excl = (offs, acc[valid])
     return torch.cat(idxs, dim=1), torch.cat(scs, dim=1)
+
+
+def topk_ip(items: torch.Tensor, queries: torch.Tensor, k: int, exclude=None):
+    """Exact inner-product top-k (faiss.IndexFlatIP.search semantics; TopKSearcher.py:50-84).
+    items [N, d], queries [Q, d] fp32 on the GPU.  `exclude` = (offsets [Q+1], item_idx) device int64
+    CSR of per-query item positions to skip (each list ascending).  Returns (idx [Q, k] int64, score
+    [Q, k] fp32): scores descending, ties toward the lower index, empty slots -1 / -FLT_MAX.
+    k > 32 runs ceil(k / 32) passes, each excluding what the earlier ones returned (same result as one
+    pass: the order (score desc, index asc) is total)."""
+    items = _f32c(items, "items")
+    queries = _f32c(queries, "queries")
+    if items.dim() != 2 or queries.dim() != 2 or items.shape[1] != queries.shape[1]:
+        raise ValueError(f"topk_ip: items {tuple(items.shape)} vs queries {tuple(queries.shape)}")
+    if k < 1:
+        raise ValueError("topk_ip: k must be >= 1")
+    if k <= TOPK_KMAX or queries.shape[0] == 0:
+        return _topk_ip_once(items, queries, k, exclude)
+    return _topk_in_passes(lambda kk, excl: _topk_ip_once(items, queries, kk, excl), queries.shape[0], queries.device, k, exclude)
 
 
 def _rows16(t: torch.Tensor, what: str) -> torch.Tensor:
@@ -2908,6 +2912,132 @@ def candidate_softmax(u: torch.Tensor, v: torch.Tensor, temperature: float = 0.1
             raise ValueError(f"candidate_softmax: {col_bias.numel()} bias values for {N} candidates")
         col_bias = col_bias.detach().contiguous()
     return _CandidateSoftmaxFn.apply(u, v, ids, col_bias, 1.0 / float(temperature), int(col_splits))[0]
+
+
+# ------------------------------------------------------------------------------- ItemCF recall (csrc/nrx_itemcf.hip)
+ITEMCF_TILE_MAX = 16384     # widest column tile of the similarity kernel: 64 KiB of int32 counters in LDS
+
+
+def _csr_pair(pair, n_lists: Optional[int], num_items: int, what: str):
+    """(offsets, items) device int tensors -> the same lists with every list sorted ascending and de-duplicated: int64 offsets and items of
+    the dtype given (int32 / int64; anything else becomes int64).  Plumbing: torch."""
+    off, items = pair
+    _dev(off, what + " offsets")
+    _dev(items, what + " items")
+    if off.is_floating_point() or items.is_floating_point():
+        raise TypeError(f"{what}: offsets and items must be integer tensors")
+    off = off.to(torch.int64).reshape(-1)
+    dtype = items.dtype if items.dtype in (torch.int32, torch.int64) else torch.int64
+    items = items.reshape(-1)
+    if off.numel() < 1 or (n_lists is not None and off.numel() != n_lists + 1):
+        raise ValueError(f"{what}: offsets must have {'n + 1' if n_lists is None else n_lists + 1} entries, got {off.numel()}")
+    n = off.numel() - 1
+    lens = off[1:] - off[:-1]
+    if int(off[0]) != 0 or int(off[-1]) != items.numel() or (n and int(lens.min()) < 0):
+        raise ValueError(f"{what}: offsets must start at 0, ascend and end at the number of items ({items.numel()})")
+    if items.numel() and (int(items.min()) < 0 or int(items.max()) >= num_items):
+        raise ValueError(f"{what}: item ids must lie in [0, {num_items})")
+    owner = torch.repeat_interleave(torch.arange(n, device=off.device), lens)
+    key = torch.unique(owner * num_items + items.to(torch.int64))            # sorted: by list, then by item
+    owner, items = torch.div(key, num_items, rounding_mode="floor"), key % num_items
+    out_off = torch.zeros(n + 1, dtype=torch.int64, device=off.device)
+    torch.cumsum(torch.bincount(owner, minlength=n), 0, out=out_off[1:])
+    return out_off, items.to(dtype).contiguous(), owner
+
+
+def _itemcf_csc(items: torch.Tensor, owner: torch.Tensor, num_items: int):
+    """The transposed CSC of a sorted CSR (items and the list each belongs to): (item_off int64 [I + 1], users, item_count int64 [I]).
+    A stable sort by item keeps every item's users ascending."""
+    order = torch.sort(items, stable=True).indices
+    users = owner[order].to(items.dtype).contiguous()
+    item_count = torch.bincount(items.to(torch.int64), minlength=num_items)
+    item_off = torch.zeros(num_items + 1, dtype=torch.int64, device=items.device)
+    torch.cumsum(item_count, 0, out=item_off[1:])
+    return item_off, users, item_count
+
+
+def _itemcf_similarity_launch(user_off, items, item_off, users, num_items: int, sim, co=None, col_tile: int = 0) -> None:
+    """The bare launch over prepared buffers (allocates nothing: capturable into a graph)."""
+    lib = _lib.load()
+    dummy = sim.data_ptr()          # an empty id array has no address of its own; it is never read
+    check(lib.nrx_itemcf_similarity(user_off.data_ptr(), items.data_ptr() or dummy, user_off.numel() - 1, item_off.data_ptr(),
+                                    users.data_ptr() or dummy, num_items, 64 if items.dtype == torch.int64 else 32, col_tile, sim.data_ptr(),
+                                    _ptr(co), None, _stream_ptr(sim)), "nrx_itemcf_similarity")
+
+
+def itemcf_similarity(user_off: torch.Tensor, items: torch.Tensor, num_items: int, return_counts: bool = False, col_tile: int = 0):
+    """Item-item co-occurrence similarity of ItemCF (recall/ItemCF/itemCF_base.py:18-40 compute_item_similarity).
+    user_off [U + 1], items: the users' histories as CSR, device int tensors (any order inside a list; an item listed twice by one user
+    counts once, as in the reference's dicts).  Returns (sim fp32 [I, I], item_count int64 [I]) and, with return_counts, the int32 [I, I]
+    co-occurrence counts:  sim_ij = c_ij / sqrt(n_i n_j) rounded once from float64, 0 where c_ij == 0 and on the diagonal.
+    ValueError when the dense matrices do not fit the device's free memory: there is no other form to fall back to."""
+    num_items = int(num_items)
+    if num_items < 1:
+        raise ValueError("itemcf_similarity: num_items must be >= 1")
+    if not 0 <= int(col_tile) <= ITEMCF_TILE_MAX:
+        raise ValueError(f"itemcf_similarity: col_tile must be in 0..{ITEMCF_TILE_MAX}")
+    u_off, u_items, owner = _csr_pair((user_off, items), None, num_items, "itemcf_similarity: histories")
+    dev = u_off.device
+    need = (8 if return_counts else 4) * num_items * num_items
+    free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+    if need > free:
+        raise ValueError(f"itemcf_similarity: the dense [{num_items}, {num_items}] result needs {need} bytes, the device has {free} free")
+    item_off, users, item_count = _itemcf_csc(u_items, owner, num_items)
+    sim =torch.empty((num_items, num_items), dtype=torch.float32, device=dev)
+    co = torch.empty((num_items, num_items), dtype=torch.int32, device=dev) if return_counts else None
+    _itemcf_similarity_launch(u_off, u_items, item_off, users, num_items, sim, co, int(col_tile))
+    return (sim, item_count, co) if return_counts else (sim, item_count)
+
+
+def itemcf_recall_workspace(num_items: int, n_queries: int, k: int, col_splits: int = 0) -> int:
+    nbytes = _lib.load().nrx_itemcf_recall_workspace(num_items, n_queries, k, col_splits)
+    if nbytes < 0:
+        raise ValueError(f"itemcf_recall: bad sizes (items {num_items}, queries {n_queries}, k {k}, col_splits {col_splits})")
+    return nbytes
+
+
+def _itemcf_recall_launch(sim, hist_off, hist_items, excl_off, excl_items, k: int, col_splits: int, out_idx, out_score, ws) -> None:
+    """The bare launch over prepared buffers (allocates nothing: capturable into a graph).  Both id arrays of one dtype."""
+    lib = _lib.load()
+    dummy = ws.data_ptr()
+    check(lib.nrx_itemcf_recall(sim.data_ptr(), sim.shape[0], hist_off.data_ptr(), hist_items.data_ptr() or dummy, excl_off.data_ptr(),
+                                excl_items.data_ptr() or dummy, 64 if hist_items.dtype == torch.int64 else 32, hist_off.numel() - 1, k,
+                                col_splits, out_idx.data_ptr(), out_score.data_ptr(), ws.data_ptr(), _stream_ptr(sim)), "nrx_itemcf_recall")
+
+
+def _itemcf_recall_once(sim, hist, excl, k, col_splits):
+    Q = hist[0].numel() - 1
+    out_idx = torch.empty((Q, k), dtype=torch.int64, device=sim.device)
+    out_score = torch.empty((Q, k), dtype=torch.float32, device=sim.device)
+    ws = torch.empty(itemcf_recall_workspace(sim.shape[0], Q, k, col_splits), dtype=torch.uint8, device=sim.device)
+    _itemcf_recall_launch(sim, hist[0], hist[1], excl[0], excl[1].to(hist[1].dtype), k, col_splits, out_idx, out_score, ws)
+    return out_idx, out_score
+
+
+def itemcf_recall(sim: torch.Tensor, hist, k: int, exclude=None, col_splits: int = 0):
+    """Top-k ItemCF recall (recall/ItemCF/itemCF_base.py:43-58 recall_top_k_items) for Q queries at once.
+    sim fp32 [I, I] on the GPU; hist = (offsets [Q + 1], items) CSR of the queries' histories; exclude = the same form (what
+    TopKSearcher.exclusion_csr makes), None = the history itself, the reference's de-duplication against what the user already has.
+    Score of item j: the fp32 sum of sim[i, j] over the history in ascending i; candidates are the items of positive score outside the
+    exclusion list.  Returns (idx [Q, k] int64, score [Q, k] fp32) ordered (score desc, index asc), empty slots -1 / -FLT_MAX; it does not
+    depend on col_splits.  k > 32 runs ceil(k / 32) passes, each excluding what the earlier ones returned, as topk_ip does."""
+    sim = _f32c(sim, "itemcf_recall: sim")
+    if sim.dim() != 2 or sim.shape[0] != sim.shape[1] or sim.shape[0] < 1:
+        raise ValueError(f"itemcf_recall: sim must be a square [I, I] matrix, got {tuple(sim.shape)}")
+    if k < 1:
+        raise ValueError("itemcf_recall: k must be >= 1")
+    num_items = sim.shape[0]
+    h_off, h_items, _ = _csr_pair(hist, None, num_items, "itemcf_recall: hist")
+    Q = h_off.numel() - 1
+    if exclude is None:
+        excl = (h_off, h_items)
+    else:
+        e_off, e_items, _ = _csr_pair(exclude, Q, num_items, "itemcf_recall: exclude")
+        excl = (e_off, e_items)
+    hist = (h_off, h_items)
+    if k <= TOPK_KMAX or Q == 0:
+        return _itemcf_recall_once(sim, hist, excl, k, col_splits)
+    return _topk_in_passes(lambda kk, ex: _itemcf_recall_once(sim, hist, ex, kk, col_splits), Q, sim.device, k, excl)
 
 
 def device_info(device: int = 0):

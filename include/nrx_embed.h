@@ -1028,6 +1028,29 @@ NRX_API int nrx_itemcf_recall(const float* sim, int64_t n_items, const int64_t* 
                       const void* excl_items, int32_t index_bits, int64_t n_queries, int32_t k, int32_t col_splits /* 0 = choose */,
                       int64_t* out_idx, float* out_score, void* workspace, void* stream);
 
+/* ---- self-attention over a short sequence (MultiHeadSelfAttention's core, src/model/model_utils/utils.py:31-40) ---------------
+ * qkv: fp32 [batch, seq, 3 C] with C = heads * head_dim and token stride qkv_ld >= 3 C floats -- what qkv_proj gives: q of head h at
+ * column h hd, k at C + h hd, v at 2 C + h hd.  out: [batch, seq, C], token stride out_ld, head h at column h hd -- what out_proj takes.
+ * g_out / g_qkv: the same two layouts.  Every row 16-byte aligned.  row_lse: fp32 [batch, heads, seq].  key_mask: null or fp32 [batch, seq]:
+ * key j of sample b takes part iff key_mask[b, j] != 0 (any non-zero weight keeps it); the rows of padded QUERIES are computed all the same.
+ *   s_ij = dot(q_i, k_j) * scale        (two fp32 fma chains, over the even and the odd e, added, then * scale)
+ *   p_ij = softmax over the kept j      (running maximum: finite for any finite input)
+ *   out_i = sum_j p_ij v_j              row_lse_i = log sum_kept exp(s_ij)
+ *   a sample with no kept key: out = 0 exactly, row_lse = -inf, its rows of g_qkv are written as 0
+ * backward (s and p recomputed from qkv and row_lse), delta_i = dot(g_out_i, out_i):
+ *   dV = P^T g_out    dP = g_out V^T    dS = P o (dP - delta)    dQ = scale dS K    dK = scale dS^T Q        (a masked key's dK, dV rows: 0)
+ * One workgroup owns one (sample, head): no buffer with a seq^2 term, no workspace, no atomics, no allocation, copy or synchronisation
+ * (capturable).  Bytes beyond a row's width inside a padded stride are never written and nothing outside the tensors is read.  The same bits
+ * run to run, and a sample's result does not depend on batch or on its place in the batch.
+ * seq in 1..128, head_dim a multiple of 4 in 4..64, C <= 256: anything else of valid form is NRX_ERR_UNSUPPORTED.  Null or misaligned
+ * pointers, strides below the row width, heads < 1, seq < 1, head_dim < 1: NRX_ERR_BAD_ARG before any launch.  batch == 0: NRX_OK, nothing
+ * launched. */
+NRX_API int nrx_attn_fwd(const float* qkv, int64_t qkv_ld, int64_t batch, int32_t seq, int32_t heads, int32_t head_dim, float scale,
+                 const float* key_mask /* or null */, float* out, int64_t out_ld, float* row_lse, void* stream);
+NRX_API int nrx_attn_bwd(const float* qkv, int64_t qkv_ld, int64_t batch, int32_t seq, int32_t heads, int32_t head_dim, float scale,
+                 const float* key_mask /* or null */, const float* out, int64_t out_ld, const float* row_lse, const float* g_out,
+                 int64_t g_out_ld, float* g_qkv, int64_t g_qkv_ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2914,6 +2914,104 @@ def candidate_softmax(u: torch.Tensor, v: torch.Tensor, temperature: float = 0.1
     return _CandidateSoftmaxFn.apply(u, v, ids, col_bias, 1.0 / float(temperature), int(col_splits))[0]
 
 
+# ------------------------------------------------------------------------------- short-sequence self-attention (csrc/nrx_attn.hip)
+SEQ_ATTENTION_MAX_SEQ = 128
+SEQ_ATTENTION_MAX_WIDTH = 256
+seq_attention_calls = 0          # forward launches of nrx_attn_fwd so far (tests assert the modules took the fused path)
+
+
+def seq_attention_supported(seq: int, num_heads: int, head_dim: int) -> bool:
+    """The shapes nrx_attn_fwd / _bwd take (anything else is NRX_ERR_UNSUPPORTED there)."""
+    return (1 <= seq <= SEQ_ATTENTION_MAX_SEQ and num_heads >= 1 and 4 <= head_dim <= 64 and head_dim % 4 == 0
+            and num_heads * head_dim <= SEQ_ATTENTION_MAX_WIDTH)
+
+
+def _tokens16(t: torch.Tensor, what: str) -> torch.Tensor:
+    """[B, N, W] fp32 on the device whose token rows the kernels read as float4s in place: unit column stride, token stride >= W and
+    % 4 == 0, sample stride = N token strides, 16-byte aligned base (a column slice of a wider buffer qualifies); else a contiguous copy."""
+    B, N, W = t.shape
+    if t.numel() == 0:
+        return t.contiguous()
+    ld = _token_ld(t)
+    ok = t.stride(2) == 1 and ld >= W and ld % 4 == 0 and (B == 1 or t.stride(0) == N * ld) and t.data_ptr() % 16 == 0
+    return t if ok else t.contiguous()
+
+
+def _token_ld(t: torch.Tensor) -> int:
+    """Token stride of a [B, N, W] tensor (a dimension of size 1 has no stride of its own to go by)."""
+    B, N, W = t.shape
+    return t.stride(1) if N > 1 else (t.stride(0) if B > 1 else W)
+
+
+class _SeqAttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, mask, heads, scale):
+        global seq_attention_calls
+        lib = _lib.load()
+        B, N, W = qkv.shape
+        C = W // 3
+        hd = C // heads
+        out = torch.empty((B, N, C), dtype=torch.float32, device=qkv.device)
+        row_lse = torch.empty((B, heads, N), dtype=torch.float32, device=qkv.device)
+        check(lib.nrx_attn_fwd(qkv.data_ptr(), _token_ld(qkv), B, N, heads, hd, scale, _ptr(mask), out.data_ptr(), C, row_lse.data_ptr(),
+                               _stream_ptr(qkv)), "nrx_attn_fwd")
+        seq_attention_calls += 1
+        ctx.save_for_backward(qkv, out, row_lse, mask)
+        ctx.cfg = (heads, hd, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        lib = _lib.load()
+        qkv, out, row_lse, mask = ctx.saved_tensors
+        heads, hd, scale = ctx.cfg
+        B, N, W = qkv.shape
+        C = heads * hd
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        g_qkv = torch.empty((B, N, W), dtype=torch.float32, device=qkv.device)
+        if B == 0:
+            return g_qkv, None, None, None
+        g = _tokens16(g_out if g_out.dtype == torch.float32 else g_out.float(), "seq_attention: g_out")
+        check(lib.nrx_attn_bwd(qkv.data_ptr(), _token_ld(qkv), B, N, heads, hd, scale, _ptr(mask), out.data_ptr(), C, row_lse.data_ptr(),
+                               g.data_ptr(), _token_ld(g), g_qkv.data_ptr(), W, _stream_ptr(qkv)), "nrx_attn_bwd")
+        return g_qkv, None, None, None
+
+
+def seq_attention(qkv: torch.Tensor, num_heads: int, key_mask: Optional[torch.Tensor] = None, scale: Optional[float] = None) -> torch.Tensor:
+    """Multi-head self-attention over a short sequence, fused: qkv [B, N, 3 C] fp32 on the GPU as nn.Linear(C, 3 C) gives it (q | k | v, each
+    split into num_heads heads of C / num_heads columns) -> out [B, N, C] in the layout the output projection takes; no permute copy and no
+    [B, H, N, N] tensor, forward or backward (nrx_attn_fwd / _bwd: one workgroup owns one (sample, head), the scores are recomputed in the
+    backward).  key_mask [B, N] (optional): key j of sample b takes part iff key_mask[b, j] != 0; padded queries are computed all the same; a
+    sample with no kept key gives zeros and zero gradients.  scale defaults to head_dim ** -0.5.  N <= 128, head_dim a multiple of 4 up to
+    64, C <= 256 (seq_attention_supported); anything else raises.  A strided view with a contiguous last dimension (token stride % 4 == 0,
+    16-byte aligned) is read in place.  Differentiable in qkv; runs on the current stream with no host synchronisation (graph-capturable);
+    the same bits run to run and whatever the batch around a sample."""
+    _dev(qkv, "seq_attention: qkv")
+    if qkv.dtype != torch.float32:
+        raise TypeError(f"seq_attention: qkv must be float32, got {qkv.dtype}")
+    if qkv.dim() != 3:
+        raise ValueError(f"seq_attention: qkv must be [batch, seq, 3 * embed_dim], got {tuple(qkv.shape)}")
+    B, N, W = qkv.shape
+    heads = int(num_heads)
+    if heads < 1 or W % (3 * heads) != 0 or W == 0:
+        raise ValueError(f"seq_attention: qkv width {W} is not 3 * num_heads ({heads}) * head_dim")
+    hd = W // (3 * heads)
+    if not seq_attention_supported(N, heads, hd):
+        raise _lib.NrxError(f"seq_attention: unsupported shape (seq {N}, heads {heads}, head_dim {hd}): seq 1..{SEQ_ATTENTION_MAX_SEQ}, head_dim % 4 == 0 "
+                            f"in 4..64, heads * head_dim <= {SEQ_ATTENTION_MAX_WIDTH}")
+    mask = None
+    if key_mask is not None:
+        mask = _dev(key_mask, "seq_attention: key_mask")
+        if tuple(mask.shape) != (B, N):
+            raise ValueError(f"seq_attention: key_mask {tuple(mask.shape)} for qkv {tuple(qkv.shape)}")
+        mask = mask.detach().to(torch.float32).contiguous()
+    scale = float(hd) ** -0.5 if scale is None else float(scale)
+    if not math.isfinite(scale):
+        raise ValueError("seq_attention: scale must be finite")
+    return _SeqAttentionFn.apply(_tokens16(qkv, "seq_attention: qkv"), mask, heads, scale)
+
+
 # ------------------------------------------------------------------------------- ItemCF recall (csrc/nrx_itemcf.hip, DESIGN 7f)
 ITEMCF_TILE_MAX = 16384     # widest column tile of the similarity kernel: 64 KiB of int32 counters in LDS
 

@@ -1051,6 +1051,35 @@ NRX_API int nrx_attn_bwd(const float* qkv, int64_t qkv_ld, int64_t batch, int32_
                  const float* key_mask /* or null */, const float* out, int64_t out_ld, const float* row_lse, const float* g_out,
                  int64_t g_out_ld, float* g_qkv, int64_t g_qkv_ld, void* stream);
 
+/* ---- target attention over a bag of table rows (DIN-style pooling of the click history by the candidate) -----------------------
+ * table: [rows, dim] fp32, or bf16 with bit 0 of `flags`.  ids: [batch, bag_len] int32 / int64 (index_bits).  mask: null or fp32
+ * [batch, bag_len].  query: fp32 [batch, dim] with row stride q_ld >= dim floats.  out / g_out / g_query: fp32 [batch, dim] with their own
+ * row strides.  lse: fp32 [batch].  g_rows: fp32 [batch * bag_len, dim], contiguous.  Every row 16-byte aligned (bf16 table rows: 8-byte).
+ * With e_l = table[ids[b, l]] widened to fp32:
+ *   entry l is kept iff mask is null or mask[b, l] != 0  (any non-zero weight keeps it); a kept entry whose id is 0 takes part with row 0
+ *   s_l  = dot(query_b, e_l) * scale    the dot product: per 4-column chunk c one fp32 chain t_c = fma(q[4c+3], e[4c+3], fma(q[4c+2], e[4c+2],
+ *          fma(q[4c+1], e[4c+1], q[4c] * e[4c]))), the chunks added as a balanced binary tree in chunk order over dim padded to 4, 8, 16, 32 or
+ *          64 columns ((t_0 + t_1) + (t_2 + t_3)) + ... -- a padded chunk is 0 -- and the sum * scale rounded on its own
+ *   p    = softmax over the kept l      (running maximum: finite for any finite input)
+ *   out_b = sum_l p_l e_l               lse_b = log sum_kept exp(s_l)
+ *   a sample with no kept entry: out = 0 exactly, lse = -inf, g_query = 0 and its rows of g_rows are 0
+ * backward, from table, ids, mask, query, out, lse and g_out alone (s and p are recomputed; nothing of size batch * bag_len is saved):
+ *   delta = dot(g_out_b, out_b)   dp_l = dot(g_out_b, e_l)   ds_l = p_l (dp_l - delta)   g_query_b = scale sum_l ds_l e_l
+ *   g_rows[b * bag_len + l] = p_l g_out_b + scale ds_l query_b      -- the gradient of lookup (b, l); zeros for an entry that is not kept
+ * Out-of-range ids never fault: the entry is read as row 0 and recorded in `status` (device int32[4] or NULL; feature 0); its g_rows row is 0.
+ * One wave owns one sample: no atomics, no workspace, no allocation, copy or synchronisation (capturable).  Bytes beyond dim inside a padded
+ * stride of out / g_query are never written.  The same bits run to run, and a sample's result does not depend on batch or on its place in it.
+ * dim a multiple of 4 in 4..64, bag_len in 1..256, rows <= 2^30: anything else of valid form is NRX_ERR_UNSUPPORTED.  Null or misaligned
+ * pointers, strides below dim, a non-finite scale, index_bits not 32 / 64, undefined flag bits, bag_len < 1, dim < 1, rows < 1:
+ * NRX_ERR_BAD_ARG before any launch.  batch == 0: NRX_OK, nothing launched. */
+NRX_API int nrx_din_pool_fwd(const void* table, int64_t rows, int32_t dim, int32_t flags /* bit 0: table is bf16 */, const void* ids,
+                     int32_t index_bits, const float* mask /* or null */, const float* query, int64_t q_ld, int64_t batch, int32_t bag_len,
+                     float scale, float* out, int64_t out_ld, float* lse, int32_t* status, void* stream);
+NRX_API int nrx_din_pool_bwd(const void* table, int64_t rows, int32_t dim, int32_t flags /* bit 0: table is bf16 */, const void* ids,
+                     int32_t index_bits, const float* mask /* or null */, const float* query, int64_t q_ld, int64_t batch, int32_t bag_len,
+                     float scale, const float* out, int64_t out_ld, const float* lse, const float* g_out, int64_t g_out_ld, float* g_query,
+                     int64_t g_query_ld, float* g_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

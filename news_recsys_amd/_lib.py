@@ -212,6 +212,8 @@ SIGNATURES = {
     "nrx_itemcf_recall": (C.c_int, [_p, _i64, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _p, _p, _p, _p]),
     "nrx_attn_fwd": (C.c_int, [_p, _i64, _i64, _i32, _i32, _i32, C.c_float, _p, _p, _i64, _p, _p]),
     "nrx_attn_bwd": (C.c_int, [_p, _i64, _i64, _i32, _i32, _i32, C.c_float, _p, _p, _i64, _p, _p, _i64, _p, _i64, _p]),
+    "nrx_din_pool_fwd": (C.c_int, [_p, _i64, _i32, _i32, _p, _i32, _p, _p, _i64, _i64, _i32, C.c_float, _p, _i64, _p, _p, _p]),
+    "nrx_din_pool_bwd": (C.c_int, [_p, _i64, _i32, _i32, _p, _i32, _p, _p, _i64, _i64, _i32, C.c_float, _p, _i64, _p, _p, _i64, _p, _i64, _p, _p]),
     "nrx_rep_pack": (C.c_int, [C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_i64), C.POINTER(_i32), _i32, C.POINTER(_i64),
                                C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32), _i32, _i32, _i64, _i64, _p, _p]),
     "nrx_rep_ordered_sum": (C.c_int, [_p, _i32, _i64, _i64, _p, _p]),

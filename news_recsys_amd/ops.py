@@ -12,6 +12,7 @@ Operator                          replaces (reference file:line)
   dcn_v1 / dcn_v1_cat_             DCNLayer / DCNNet (+ torch.cat of dcn/model.py:29)  dcn/dcn_arch.py:14-30,63-70
   dcn_v2                           DCNv2Layer / DCNv2Net                dcn/dcn_arch.py:33-50,73-91
   bucketize_by_owner, gather_rows_segmented, mask_lengths   (new: row-sharded tables)
+  din_pool                         (new: target attention over the click history)
   itemcf_similarity / itemcf_recall  compute_item_similarity / recall_top_k_items  recall/ItemCF/itemCF_base.py:18-58
 """
 from __future__ import annotations
@@ -475,6 +476,10 @@ def _small_shapes_uncached(plan, B) -> bool:
     return bool(per) and max(per.values()) <= 4096
 
 
+_BF16_NEEDS_SINK = ("bf16 embedding tables train only through the row-sparse sink (sparse_grad=SparseGradSink, "
+                    "optim.FusedSparseAdam): dense or COO gradients of a bf16 table are not formed")
+
+
 class _EmbedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan: EmbedPlan, inputs, weights, out_ld, need_out, sparse_grad, index_check, *tables):
@@ -484,8 +489,7 @@ class _EmbedFn(torch.autograd.Function):
         ctx.sparse_grad = bool(sparse_grad)
         ctx.tables = list(tables) if ctx.sink is not None else None
         if ctx.sink is None and any(t.dtype is torch.bfloat16 and g for t, g in zip(tables, ctx.needs_input_grad[7:])):
-            raise NotImplementedError("bf16 embedding tables train only through the row-sparse sink (sparse_grad=SparseGradSink, "
-                                      "optim.FusedSparseAdam): dense or COO gradients of a bf16 table are not formed")
+            raise NotImplementedError(_BF16_NEEDS_SINK)
         if sparse_grad and any(s.flags & NRX_FEAT_ROW0_IS_DATA for s in plan.slots):
             raise NotImplementedError("sparse_grad: the sorted backward treats row 0 of every table as the padding row; "
                                       "a feature flagged NRX_FEAT_ROW0_IS_DATA (routed-row buffers) needs the dense-gradient mode")
@@ -3010,6 +3014,178 @@ def seq_attention(qkv: torch.Tensor, num_heads: int, key_mask: Optional[torch.Te
     if not math.isfinite(scale):
         raise ValueError("seq_attention: scale must be finite")
     return _SeqAttentionFn.apply(_tokens16(qkv, "seq_attention: qkv"), mask, heads, scale)
+
+
+# ------------------------------------------------------------------------------- target-attention pooling (csrc/nrx_din.hip)
+DIN_POOL_MAX_LEN = 256
+DIN_POOL_MAX_DIM = 64
+din_pool_calls = 0               # forward launches of nrx_din_pool_fwd so far (tests assert the model took the fused path)
+_DIN_NAMES = ["din_pool"]        # the one "feature" of the launch in an IndexError
+_din_plans = {}
+
+
+def din_pool_supported(bag_len: int, dim: int) -> bool:
+    """The shapes nrx_din_pool_fwd / _bwd take (anything else is NRX_ERR_UNSUPPORTED there)."""
+    return 1 <= bag_len <= DIN_POOL_MAX_LEN and 4 <= dim <= DIN_POOL_MAX_DIM and dim % 4 == 0
+
+
+class _LookupGradRecord:
+    """What _EmbedFn._finish fills and _EmbedFn.backward reads of its ctx, for a node that makes the per-lookup row gradients itself: the
+    table then gets exactly what a single-valued feature over the same flat ids would get from that upstream gradient, in every mode."""
+    saved_tensors = ()
+
+    def __init__(self, needs_table_grad: bool, sparse_grad, tables):
+        self.needs_input_grad = (False,) * 7 + (bool(needs_table_grad),)
+        self.sink = sparse_grad if isinstance(sparse_grad, SparseGradSink) else None
+        self.sparse_grad = bool(sparse_grad)
+        self.tables = list(tables) if self.sink is not None else None
+        self.narrow = False
+
+    def save_for_backward(self, *tensors):
+        pass
+
+    def set_materialize_grads(self, value):
+        pass
+
+
+def _din_lookup_plan(table: torch.Tensor) -> EmbedPlan:
+    """The one-slot NRX_SPARSE plan of the flat lookups (kept per table shape: the backward's launch-group caches live on it)."""
+    bf16 = table.dtype is torch.bfloat16
+    key = (table.shape[0], table.shape[1], bf16)
+    plan = _din_plans.get(key)
+    if plan is None:
+        if len(_din_plans) > 64:
+            _din_plans.clear()
+        plan = _din_plans[key] = EmbedPlan([Slot("din_pool", NRX_SPARSE, 0, table.shape[1], 0, 0, flags=NRX_FEAT_TABLE_BF16 if bf16 else 0)],
+                                           out_width=table.shape[1])
+    return plan
+
+
+class _DinPoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, table, ids, query, mask, scale, sparse_grad, index_check):
+        global din_pool_calls
+        lib = _lib.load()
+        mode = index_check or _INDEX_CHECK
+        B, L = ids.shape
+        D = table.shape[1]
+        dev = table.device
+        sink = sparse_grad if isinstance(sparse_grad, SparseGradSink) else None
+        if table.dtype is torch.bfloat16 and ctx.needs_input_grad[0] and sink is None:
+            raise NotImplementedError(_BF16_NEEDS_SINK)
+        out = torch.empty((B, D), dtype=torch.float32, device=dev)
+        lse = torch.empty((B,), dtype=torch.float32, device=dev)
+        if mode == "deferred":
+            status = _deferred_status(_DIN_NAMES)
+        else:
+            status = torch.zeros(4, dtype=torch.int32, device=dev) if mode != "off" else None
+        q_ld = query.stride(0) if B > 1 else D
+        check(lib.nrx_din_pool_fwd(table.data_ptr(), table.shape[0], D, 1 if table.dtype is torch.bfloat16 else 0, ids.data_ptr(),
+                                   ids.element_size() * 8, _ptr(mask), query.data_ptr(), q_ld, B, L, scale, out.data_ptr(), D, lse.data_ptr(),
+                                   _ptr(status), _stream_ptr(table)), "nrx_din_pool_fwd")
+        din_pool_calls += 1
+        if status is not None and mode != "deferred":
+            if mode == "sync":
+                _raise_if_oob(status, _DIN_NAMES)
+            else:
+                ev = torch.cuda.Event()
+                ev.record()
+                _pending_status.append((status, ev, _DIN_NAMES))
+                while _pending_status and _pending_status[0][1].query():
+                    st, _, nm = _pending_status.pop(0)
+                    _raise_if_oob(st, nm)
+        ctx.rec = None
+        if ctx.needs_input_grad[0]:
+            # the table's gradient: the backward's g_rows is the upstream gradient of a single-valued feature over the B * L flat ids
+            ctx.rec = rec = _LookupGradRecord(True, sparse_grad, (table,))
+            _EmbedFn._finish(rec, _din_lookup_plan(table), (table,), B * L, D, [ids.view(-1)], [None], None, None, None, None, True, False)
+        ctx.save_for_backward(table, ids, query, mask, out, lse)
+        ctx.scale = scale
+        ctx.mark_non_differentiable(lse)
+        return out, lse
+
+    @staticmethod
+    def backward(ctx, g_out, _g_lse):
+        lib = _lib.load()
+        table, ids, query, mask, out, lse = ctx.saved_tensors
+        if g_out is None or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[2]):
+            return (None,) * 7
+        B, L = ids.shape
+        D = table.shape[1]
+        dev = table.device
+        g = _rows16(g_out if g_out.dtype == torch.float32 else g_out.float(), "din_pool: g_out")
+        g_query = torch.empty((B, D), dtype=torch.float32, device=dev)
+        g_rows = torch.empty((B * L, D), dtype=torch.float32, device=dev)
+        check(lib.nrx_din_pool_bwd(table.data_ptr(), table.shape[0], D, 1 if table.dtype is torch.bfloat16 else 0, ids.data_ptr(),
+                                   ids.element_size() * 8, _ptr(mask), query.data_ptr(), query.stride(0) if B > 1 else D, B, L, ctx.scale,
+                                   out.data_ptr(), D, lse.data_ptr(), g.data_ptr(), g.stride(0) if B > 1 else D, g_query.data_ptr(), D,
+                                   g_rows.data_ptr(), _stream_ptr(table)), "nrx_din_pool_bwd")
+        g_table = None
+        if ctx.rec is not None:
+            g_table = _EmbedFn.backward(ctx.rec, g_rows, None, None)[7]       # (None with a sink: the rows went there)
+        return g_table, None, (g_query if ctx.needs_input_grad[2] else None), None, None, None, None
+
+
+def din_pool(table: torch.Tensor, ids: torch.Tensor, query: torch.Tensor, mask: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+             sparse_grad=False, index_check: Optional[str] = None, return_lse: bool = False):
+    """Target attention over a bag of table rows, fused into the gather (DIN-style pooling of a click history by the candidate): table [rows, D]
+    fp32 or bf16, ids [B, L] int32 / int64, query [B, D] fp32 -> out [B, D] = sum_l softmax_l(dot(query_b, table[ids[b, l]]) * scale)
+    table[ids[b, l]] over the entries with mask[b, l] != 0 (mask None: all of them).  Neither [B, L, D] rows nor [B, L] scores are
+    materialised in the forward; the backward makes the per-lookup gradients g_rows [B * L, D] in one launch and hands them to the embedding
+    backward as the upstream gradient of a single-valued feature over the flat ids, so the table trains in every mode embed_apply has: dense
+    .grad by default, COO with sparse_grad=True, a SparseGradSink entry with a sink (bf16 tables: the sink only); row 0 never receives
+    gradient.  A sample with no kept entry gives zeros and zero gradients.  scale defaults to D ** -0.5.  L in 1..256, D a multiple of 4 in
+    4..64 (din_pool_supported); anything else raises.  query may be a column slice of a wider buffer (unit column stride, row stride
+    % 4 == 0, 16-byte aligned: read in place; else a contiguous copy).  Out-of-range ids: as embed_apply (index_check), the entry reads row 0.
+    Differentiable in table and query; runs on the current stream (no host synchronisation unless index_check is 'sync'); the same bits run
+    to run and whatever the batch around a sample.  return_lse: also the [B] log-sum-exp of the kept scores (-inf for an empty sample)."""
+    _dev(table, "din_pool: table")
+    _dev(ids, "din_pool: ids")
+    if table.dim() != 2 or not table.is_contiguous() or table.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("din_pool: table must be a contiguous [rows, dim] fp32 or bf16 tensor")
+    if ids.dim() != 2 or ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"din_pool: ids must be [batch, bag_len] int32 or int64, got {tuple(ids.shape)} {ids.dtype}")
+    B, L = ids.shape
+    D = table.shape[1]
+    if query.dim() != 2 or tuple(query.shape) != (B, D):
+        raise ValueError(f"din_pool: query {tuple(query.shape)} for ids {tuple(ids.shape)} and table dim {D}")
+    if not din_pool_supported(L, D):
+        raise _lib.NrxError(f"din_pool: unsupported shape (bag_len {L}, dim {D}): bag_len 1..{DIN_POOL_MAX_LEN}, dim % 4 == 0 in 4..{DIN_POOL_MAX_DIM}")
+    query = _rows16(query, "din_pool: query")
+    if mask is not None:
+        mask = _dev(mask, "din_pool: mask")
+        if tuple(mask.shape) != (B, L):
+            raise ValueError(f"din_pool: mask {tuple(mask.shape)} for ids {tuple(ids.shape)}")
+        mask = mask.detach().to(torch.float32).contiguous()
+    scale = float(D) ** -0.5 if scale is None else float(scale)
+    if not math.isfinite(scale):
+        raise ValueError("din_pool: scale must be finite")
+    out, lse = _DinPoolFn.apply(table, ids.contiguous(), query, mask, scale, sparse_grad, index_check)
+    return (out, lse) if return_lse else out
+
+
+def din_pool_math(table: Optional[torch.Tensor], ids: Optional[torch.Tensor], query: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                  scale: Optional[float] = None, rows: Optional[torch.Tensor] = None, return_lse: bool = False):
+    """din_pool's definition in plain torch, on any device and in the dtype of `query` (the fallback and the yardstick): rows [B, L, D] --
+    table[ids] unless they are handed in (e.g. from get_feature_embedding) -- scores, a masked softmax that gives zeros for a sample with no
+    kept entry, the weighted sum.  Differentiable by autograd."""
+    e = (table[ids.long()] if rows is None else rows).to(query.dtype)
+    D = e.shape[-1]
+    scale = float(D) ** -0.5 if scale is None else float(scale)
+    s = (e * query.unsqueeze(1)).sum(-1) * scale
+    if mask is not None:
+        s = s.masked_fill(mask == 0, float("-inf"))
+    m = s.max(dim=1, keepdim=True).values
+    m = torch.where(torch.isinf(m), torch.zeros_like(m), m).detach()
+    ex = torch.exp(s - m)
+    den = ex.sum(dim=1, keepdim=True)
+    some = den > 0
+    p = torch.where(some, ex / torch.where(some, den, torch.ones_like(den)), torch.zeros_like(ex))
+    out = (p.unsqueeze(-1) * e).sum(1)
+    if return_lse:
+        lse = torch.where(some, m + torch.log(torch.where(some, den, torch.ones_like(den))), torch.full_like(den, float("-inf")))
+        return out, lse.squeeze(1).detach()
+    return out
 
 
 # ------------------------------------------------------------------------------- ItemCF recall (csrc/nrx_itemcf.hip, DESIGN 7f)

@@ -841,6 +841,9 @@ def shard_model_step_(model, rank: int, world: int, group=None, host_staged: boo
     rounds stochastically with the GLOBAL row in its hash (configure_optimizers() wires arena_row_map), so after every optimizer step the
     arenas hold the bf16 bit patterns of the unsharded bf16 model trained on the rank-major concatenation of the batches.  A bf16 model
     without it is refused (the conversion is opt-in), an fp32 model with it is a ValueError."""
+    if getattr(model, "din_cfg", None) is not None:
+        raise NotImplementedError("shard_model_step_: a model with din_cfg (sort/din: target-attention pooling of the history) is not supported -- the "
+                                  "bound step's routing does not know that operator")
     is_bf16 = [e.weight.dtype is torch.bfloat16 for e in model.embedding_tables.values()]
     if any(is_bf16) and not bf16_tables:
         raise NotImplementedError("shard_model_step_: the model's embedding tables are bf16 (embeddings.table_dtype: bf16): pass bf16_tables=True "

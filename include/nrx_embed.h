@@ -801,7 +801,8 @@ NRX_API int nrx_scatter_add_inbox(float* const* grad_tables, const int64_t* tabl
  *                          in source order (deterministic, no atomics); every element of partial
  *                          [world, n_feats*batch, dim] is written; workspace: nrx_pool_inbox_workspace(...) device bytes
  *   nrx_pool_inbox_bwd     owner: grad_table[row] += w * g_partial[s][tag][:] per entry (fp32 atomics; skip_row0 as in
- *                          nrx_scatter_add_inbox)
+ *                          nrx_scatter_add_inbox); an entry whose tag lies outside [0, n_feats*batch) is ignored, as the
+ *                          forward's marking pass and nrx_pool_inbox_expand / _owner_ids ignore it
  * The source finishes with an NRX_BAG_SUM of bag_len = world over the returned slabs (rows o*n_feats*batch + tag).  */
 NRX_API int nrx_bag_norm_weights(const float* mask, int64_t batch, int32_t bag_len, int32_t kind, float* out_w, void* stream);
 /* nrx_bag_norm_weights that also leaves out_inv[b]: the weight every live entry of sample b carries when the mask is 0 / 1 (1 / (sum w + 1e-8), 0

@@ -727,8 +727,9 @@ __global__ __launch_bounds__(NRX_BLOCK) void pool_inbox_bwd_kernel(const PoolArg
     const int32_t row = nrx_gconst<int32_t>(a->inbox_rows)[base + j];
     const float w = nrx_gconst<float>(a->inbox_w)[base + j];
     const int D = a->dim;
+    if ((uint32_t)tag >= (uint64_t)(a->n_feats * a->batch)) return;      // no (feature, sample): skipped by the marking pass, unused in the expansion
     const int f = (int)(tag / a->batch);
-    const int tix = a->feat_table[f < a->n_feats ? f : 0];
+    const int tix = a->feat_table[f];
     if ((uint32_t)row >= (uint64_t)a->rows[tix]) return;      // reported by the forward
     if (a->skip_row0 && row == 0) return;
     const float* g = a->partial + ((int64_t)s * a->n_feats * a->batch + tag) * D;

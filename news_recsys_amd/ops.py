@@ -916,7 +916,8 @@ def sparse_plan(ids: Sequence[torch.Tensor], table_of: Sequence[int], rows: Sequ
     counts [n_tables+2]); only the first counts[0] entries of uniq_keys / counts[0]+1 of seg_start are
     meaningful.  No host synchronisation.
     place_feats (bit mask over the features, see place_mask): nrx_sparse_plan_place -- three more device tensors, dest
-    int32 [n] (unique index of a lookup whose row is looked up once, else -1), walk int32 [n] (the other unique rows)
+    int32 [n] (unique index of a lookup whose row is looked up once, else -1; written for the lookups of the features in place_feats
+    ONLY -- the other words keep whatever the fresh allocation held and are no destinations), walk int32 [n] (the other unique rows)
     and n_walk int64 [1]: what nrx_embed_bwd_placed consumes.
     policy (PlanPolicy of the launch group): when it picks the one-kernel planner (nrx_sparse_plan_lds) the result has EIGHT entries -- the
     seven above (order / seg defined for the walk rows only; n_walk int64 [2]: walk rows, pair records) plus pairs int32 [n / 2 + 1, 4], the

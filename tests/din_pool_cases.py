@@ -32,10 +32,13 @@ def bf16_round(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(torch.bfloat16).to(torch.float32).numpy()
 
 
-def make_case(i, amp=1.0):
+def make_case(i, amp=1.0, **over):
     """Numpy inputs of case i: table [97, D] fp32 (bf16-representable when the case's table is bf16; row 0 zero), ids [B, L], mask or None,
-    query and g_out [B, D], scale."""
+    query and g_out [B, D], scale.  over: parameters of case_params to replace (B=..., bf16=..., mask=...): the same generator at another
+    batch size or crossing."""
     c = case_params(i)
+    assert set(over) <= set(c), over
+    c.update(over)
     L, D, B = c["L"], c["D"], c["B"]
     rng = np.random.default_rng(1000 + i)
     table = (rng.standard_normal((ROWS, D)) * amp).astype(np.float32)

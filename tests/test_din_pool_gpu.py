@@ -13,6 +13,7 @@ from tests import din_pool_ref as R
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 SENTINEL = -77.25
+DN_MAX_BLOCKS, DN_WAVES = 2048, 4                    # csrc/nrx_din.hip: din_grid()'s cap, samples (waves) per workgroup
 
 
 def _dev_case(c, table=None):
@@ -178,6 +179,35 @@ def test_bits_run_to_run_sample_alone_and_graph_replay():
     torch.cuda.synchronize()
     for k in ("out", "lse", "g_query", "g_rows"):
         assert torch.equal(a[k], g[k]), k
+
+
+@pytest.mark.parametrize("i,over", [(14, {}), (17, dict(bf16=True, mask="holes"))], ids=["L3-D4", "L17-D16-bf16-holes"])
+def test_a_wave_that_strides_to_a_second_sample(i, over):
+    """din_grid() caps a launch at DN_MAX_BLOCKS = 2048 workgroups of 4 waves: from batch 8193 on a wave takes a second sample, whose ids it
+    requested BEFORE it consumed the first (nxt = dn_load_ids(b + stride); cur = nxt) -- in the forward and in the backward kernel.
+    B = 8192 + 4 + 3: seven waves take a second trip, four of them in one whole workgroup, three in a workgroup whose fourth wave is done.
+    Against the float64 reference within its bounds, like every case; and samples 0..6 (first trip) and 8192..8198 (second trip, produced by
+    the strided pass alone) give the same bits when each is run alone."""
+    B = DN_MAX_BLOCKS * DN_WAVES + 4 + 3
+    c = cases.make_case(i, B=B, **over)
+    assert c["ids"].shape == (B, c["L"]) and (c["L"], c["D"]) in ((3, 4), (17, 16))
+    D, L = c["D"], c["L"]
+    ref = R.din_pool_ref(c["table"], c["ids"], c["mask_arr"], c["query"], c["scale"], c["g_out"])
+    bnd = R.bounds(ref, c["table"], c["query"], c["scale"])
+    got = run_kernels(c, 4)
+    torch.cuda.synchronize()
+    check_against_ref(c, got, ref, bnd, D, f"stride-{cases.case_id(i)}-B{B}")
+    assert _pads_untouched(got["out"], D) and _pads_untouched(got["g_query"], D)
+    second = slice(DN_MAX_BLOCKS * DN_WAVES, B)                          # what only the second trip produces, held to the reference on its own
+    tail = {k: (v[second] if k != "g_rows" else v[second.start * L:]) for k, v in got.items() if k in ("out", "lse", "g_query", "g_rows")}
+    check_against_ref(c, tail, {k: v[second] for k, v in ref.items()}, {k: v[second] for k, v in bnd.items()}, D, "second trip")
+    plain = run_kernels(c, 0)
+    for s in list(range(7)) + list(range(second.start, B)):
+        one = dict(c, ids=c["ids"][s:s + 1], mask_arr=None if c["mask_arr"] is None else c["mask_arr"][s:s + 1], query=c["query"][s:s + 1],
+                   g_out=c["g_out"][s:s + 1])
+        g = run_kernels(one, 0)
+        assert torch.equal(g["out"][0], plain["out"][s]) and torch.equal(g["lse"][0], plain["lse"][s]), s
+        assert torch.equal(g["g_query"][0], plain["g_query"][s]) and torch.equal(g["g_rows"], plain["g_rows"][s * L:(s + 1) * L]), s
 
 
 def _sink_dense(sink, rows, D):

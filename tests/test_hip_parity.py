@@ -1602,11 +1602,13 @@ def test_dense_value_mid_order_keeps_later_features_on_the_ring_kernel(B, idx, m
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("B", [1, 1000, 65536 + 3])
+@pytest.mark.parametrize("B", [1, 1000, 65536 + 3, 262144 + 5])
 def test_fm_head_forward_and_backward_vs_float64(B):
     """ops.fm_head = the last line of FMModel.forward, sigmoid(bias + first + second) (src/model/sort/fm/model.py:25-26), and its autograd: one
     launch each way.  Against torch in float64 (forward rtol 1e-6; gradients rtol 1e-5), with a per-sample upstream gradient and with the expanded
-    scalar a `.sum()` hands down (read once, not materialised); the bias gradient is summed in a fixed order: same bits run to run."""
+    scalar a `.sum()` hands down (read once, not materialised); the bias gradient is summed in a fixed order: same bits run to run.
+    nrx_fm_head_fwd caps its grid at 1024 blocks of 256 samples: B = 262144 + 5 gives the stride loop a second trip, whose five samples
+    (and their gradients) are compared like every other -- and once more on their own below."""
     from news_recsys_amd import ops
     gen = torch.Generator(device="cuda:0").manual_seed(B)
     logit = (torch.randn(B, device="cuda:0", generator=gen) * 3).requires_grad_()
@@ -1619,6 +1621,9 @@ def test_fm_head_forward_and_backward_vs_float64(B):
     torch.testing.assert_close(out.double(), ref, rtol=1e-6, atol=1e-7)
     (ref * up.double()).sum().backward()
     (out * up).sum().backward()
+    if B > 262144:                                       # the second trip of the capped grid alone
+        torch.testing.assert_close(out[262144:].double(), ref[262144:], rtol=1e-6, atol=1e-7)
+        torch.testing.assert_close(logit.grad[262144:].double(), l64.grad[262144:], rtol=1e-5, atol=1e-6)
     # (p (1 - p) from the SAVED fp32 p, as torch's sigmoid_backward forms it: where p rounds towards 1 the factor 1 - p carries p's rounding, an
     # absolute error of ~1e-7 on a gradient of ~1e-3 -- hence the absolute term)
     torch.testing.assert_close(logit.grad.double(), l64.grad, rtol=1e-5, atol=1e-6)

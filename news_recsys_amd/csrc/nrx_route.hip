@@ -457,9 +457,14 @@ __global__ __launch_bounds__(NRX_BLOCK) void inbox_gather_ring_kernel(const Inbo
         // (resolving inside the walk put a ~6-step dependent chain in front of every load: 113 us instead of 85)
         __syncthreads();                                     // (the previous work item's readers are done)
         const NRX_GLOBAL int32_t* inb = nrx_gconst<int32_t>(a->inbox) + s * cap + base;
+        // (NS * TB positions: whole trips of the block for TB >= 8; at TB = 4 -- rows of 132..256 floats -- the item has 128 slots and half
+        // the block resolves them in one trip.  Counted as NS * TB / NRX_BLOCK, that width took no trip, resolved nothing and walked stale
+        // LDS words.  The partial-trip test is a compile-time constant: the other widths keep their instruction stream.)
+        constexpr int RESOLVE_TRIPS = (NS * TB + NRX_BLOCK - 1) / NRX_BLOCK;
 #pragma unroll
-        for (int i = 0; i < NS * TB / NRX_BLOCK; ++i) {
+        for (int i = 0; i < RESOLVE_TRIPS; ++i) {
             const int pos = i * NRX_BLOCK + threadIdx.x;
+            if ((NS * TB) % NRX_BLOCK != 0 && pos >= NS * TB) break;
             const int64_t j = base + pos;
             const float* ptr = nullptr;
             float* dst = nullptr;

@@ -53,6 +53,14 @@ static inline bool nrx_table_aligned(const nrx_feature_t& s) {
     return (reinterpret_cast<uintptr_t>(s.table) & ((s.flags & NRX_FEAT_TABLE_BF16) ? 7u : 15u)) == 0;
 }
 
+// Lane-group width of the row-list kernels (nrx_row_optim.hip, nrx_gradnorm.hip): Q = 2^ql lanes walk one row, the smallest Q with
+// 4 Q >= dim (one float4 per lane), a wavefront at the most.
+static inline int nrx_row_qlog2(int dim) {
+    int ql = 0;
+    while ((4 << ql) < dim && ql < 6) ++ql;
+    return ql;
+}
+
 // Device-side feature descriptor (48 B; 64 of them fit the 4 KiB kernarg segment).
 struct FeatDev {
     const float* table;   // weight table, or grad table in the backward

@@ -226,8 +226,7 @@ extern "C" int nrx_rows_sqnorm(const int64_t* uniq_keys, const float* grads, int
     a.n_tables = n_tables;
     a.dim = dim;
     const bool vec = (dim & 3) == 0 && nrx_aligned16(grads);
-    int ql = 0;
-    while ((4 << ql) < dim && ql < 6) ++ql;
+    const int ql = nrx_row_qlog2(dim);
     const int tb = NRX_BLOCK >> ql;
     const int64_t groups = (n + 3) / 4;                          // 4 rows per lane group and pass
     const int64_t blocks = (groups + tb - 1) / tb;

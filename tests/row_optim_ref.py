@@ -1,4 +1,4 @@
-"""float64 numpy restatements of the row-optimizer kernels of nrx_sparse.hip (include/nrx_embed.h), and the hand-made key lists their tests run on.
+"""float64 numpy restatements of the row-optimizer kernels of nrx_row_optim.hip (include/nrx_embed.h), and the hand-made key lists their tests run on.
 No GPU, no torch: tests/test_row_optim_ref.py holds these against torch's float64 optimizers on the CPU, tests/test_row_optimizer_kernels_gpu.py
 holds the kernels against these.
 

@@ -5,7 +5,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ROOT  := $(abspath $(dir $(lastword $(MAKEFILE_LIST)))/../..)
 CSRC  := $(ROOT)/news_recsys_amd/csrc
 OUT   := $(ROOT)/tests/sanitize/_build
-UNITS := nrx_lib nrx_sparse
+UNITS := nrx_lib nrx_row_optim
 # (the sanitizer flags and -fno-gpu-sanitize stay on one line: the device code is never instrumented)
 FLAGS := --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -munsafe-fp-atomics -I$(ROOT)/include -fno-omit-frame-pointer -Wno-unused-function
 FLAGS += -fsanitize=address,undefined -fno-sanitize-recover=all -fno-gpu-sanitize

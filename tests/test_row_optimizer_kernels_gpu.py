@@ -1,12 +1,13 @@
-"""The row-optimizer kernels of nrx_sparse.hip ALONE, through ctypes, against the float64 restatements of tests/row_optim_ref.py (themselves held to
+"""The row-optimizer kernels of nrx_row_optim.hip ALONE, through ctypes, against the float64 restatements of tests/row_optim_ref.py (themselves held to
 torch's float64 optimizers by tests/test_row_optim_ref.py):
 
   nrx_sparse_adam_step                 every lane-group width, the dim > 256 column loop, the float4 and the element-by-element form, both moment
                                        layouts ([rows, 2, dim] and separate arrays), lists of one entry up to three blocks, a device-side count
-  nrx_sparse_adam_step_bf16 / _rows    moments = the fp32 call's bits, patterns = tests/sr_bf16_ref.py's rounding of the fp32 call's weights
+  nrx_sparse_adam_step_bf16 / _rows    moments = the fp32 call's bits, patterns = tests/sr_bf16_ref.py's rounding of the fp32 call's weights: every
+                                       lane-group width, lists of one to five entries, the element-by-element form at a four-column dim
   nrx_rows_mark + nrx_dense_adamw_rows several blocks per table, a one-row table, a ragged last block, two steps, hyper_dev
   nrx_rows_mark + nrx_rows_merge       bit for bit (one fp32 addition per shared row), then the whole merged step against float64
-  nrx_rows_to_dense                    store and accumulate forms on long lists
+  nrx_rows_to_dense                    store and accumulate forms on long lists and on lists shorter than a lane group's four entries
 
 Every buffer a kernel may write sits inside a larger buffer of guard bytes that must come back untouched, and every row no live key names must keep
 its bits (compared as integers) -- the padding row, the row of the entry past the device-side count, the neighbours of a named row.
@@ -225,26 +226,26 @@ def test_sparse_adam_step_size_on_the_device_overrides_the_host_value(dim):
     b.check_guards_and_inputs()
 
 
-@pytest.mark.parametrize("mapped", [False, True])
-@pytest.mark.parametrize("inter", [True, False])
-@pytest.mark.parametrize("dim", [1, 6, 32, 112, 320])
-def test_sparse_adam_bf16_is_the_fp32_call_rounded_by_the_restated_stream(dim, inter, mapped):
-    """The fp32 call on the widened table is held to float64 by the test above (same inputs up to the widening: checked here again); the bf16 call
-    must leave its moments bit for bit and sr_round of its weights, the rounding stream hashed on the MAPPED row."""
-    n, seed, step = long_n(dim), 0xDEADBEEF12345, 7
-    ref = AdamCase(dim, n, inter, bf16_values=True).run()
+def _bf16_adam_is_the_fp32_call_rounded(dim, n, inter, maps, mis=None):
+    """The fp32 call on the widened table is held to float64 (same inputs up to the widening, same `mis`: both calls take the same form of the
+    kernel); the bf16 call must leave its moments bit for bit and sr_round of its weights, the rounding stream hashed on the MAPPED row.
+    A long list (n >= 37) names at least three rows of every table; a short one names what check_against_float64 finds from the reference alone,
+    at least one row."""
+    seed, step = 0xDEADBEEF12345, 7
+    mapped = maps is not None
+    ref = AdamCase(dim, n, inter, bf16_values=True, mis=mis).run()
     ref.check_against_float64()
     w32, m32, v32 = ref.read()
-    maps = AdamCase.MAPS if mapped else None
-    first = AdamCase(dim, n, inter, store_bf16=True)
+    first = AdamCase(dim, n, inter, store_bf16=True, mis=mis)
     step_dev = Guarded(np.array([step], dtype=np.int64))
     if mapped:
         first.run("nrx_sparse_adam_step_bf16_rows", seed=seed, step=step, maps=maps)
     else:
         first.run("nrx_sparse_adam_step_bf16", seed=seed, step=step)
     # the device-side step overrides a wrong host step; the row-mapped entry with NULL maps is the identity
-    second = AdamCase(dim, n, inter, store_bf16=True).run("nrx_sparse_adam_step_bf16_rows", seed=seed, step=step + 1000, step_dev=step_dev, maps=maps)
+    second = AdamCase(dim, n, inter, store_bf16=True, mis=mis).run("nrx_sparse_adam_step_bf16_rows", seed=seed, step=step + 1000, step_dev=step_dev, maps=maps)
     named, cols = ref.named(), np.arange(dim)
+    assert sum(len(x) for x in named) >= 1
     for case in (first, second):
         got_w, got_m, got_v = case.read()
         for t in range(3):
@@ -257,12 +258,45 @@ def test_sparse_adam_bf16_is_the_fp32_call_rounded_by_the_restated_stream(dim, i
             mul, add = maps[t] if mapped else (1, 0)
             want = SR.sr_round(w32[t][rows], SR.sr_bits(seed, step, t, rows * mul + add, cols))
             assert SR.matches(got_w[t][rows], want), f"table {t}: bf16 patterns != (f32_bits(w_new) + bits16) >> 16"
-            assert rows.size >= 3
-            assert not np.array_equal(got_w[t][rows], before[rows])
-            if mapped and t != 1:            # (so the test sees the map: the unmapped stream gives other patterns)
+            assert rows.size >= (3 if n >= 37 else 0)
+            if rows.size:
+                assert not np.array_equal(got_w[t][rows], before[rows])
+            # (so the test sees the map: the unmapped stream gives other patterns -- asked where there are enough elements, 256 and more, that
+            # two streams cannot round them all alike: every table of a long list)
+            if mapped and (mul, add) != (1, 0) and rows.size * dim >= 256:
                 assert not SR.matches(got_w[t][rows], SR.sr_round(w32[t][rows], SR.sr_bits(seed, step, t, rows, cols)))
+            assert n < 37 or not mapped or t == 1 or rows.size * dim >= 256
         case.check_guards_and_inputs()
     assert step_dev.intact()
+
+
+@pytest.mark.parametrize("mapped", [False, True])
+@pytest.mark.parametrize("inter", [True, False])
+@pytest.mark.parametrize("dim", [1, 6, 32, 112, 320])
+def test_sparse_adam_bf16_is_the_fp32_call_rounded_by_the_restated_stream(dim, inter, mapped):
+    _bf16_adam_is_the_fp32_call_rounded(dim, long_n(dim), inter, AdamCase.MAPS if mapped else None)
+
+
+@pytest.mark.parametrize("mapped", [False, True])
+@pytest.mark.parametrize("n", [1, 3, 4, 5])
+@pytest.mark.parametrize("dim", [6, 16, 320])
+def test_sparse_adam_bf16_on_short_lists(dim, n, mapped):
+    """A partial group of four entries in the element-by-element (dim 6) and the four-column body; at n = 5 the last lane group holds one key.  A
+    short list names rows of table 1 only, so its map is not the identity here."""
+    _bf16_adam_is_the_fp32_call_rounded(dim, n, False, [(3, -1), (2, 7), (2, 5)] if mapped else None)
+
+
+@pytest.mark.parametrize("dim", [4, 8, 16, 64, 128, 516])
+def test_sparse_adam_bf16_at_the_remaining_lane_group_widths(dim):
+    """With the dims of the test above: 1, 2, 4, ... 64 lanes per row, and at 516 a second trip of the column loop."""
+    _bf16_adam_is_the_fp32_call_rounded(dim, long_n(dim), True, None)
+
+
+@pytest.mark.parametrize("mapped", [False, True])
+@pytest.mark.parametrize("dim", [16, 320])
+def test_sparse_adam_bf16_on_misaligned_gradients_takes_the_element_form_of_the_fp32_call(dim, mapped):
+    """Gradients 4 bytes off a 16-byte boundary, in the fp32 call too: both take the element-by-element form at a dim the four-column form serves."""
+    _bf16_adam_is_the_fp32_call_rounded(dim, long_n(dim), True, AdamCase.MAPS if mapped else None, mis="g")
 
 
 # ------------------------------------------------------------------------------------------------ nrx_rows_mark + nrx_dense_adamw_rows
@@ -490,30 +524,49 @@ def test_rows_mark_and_merge_fold_list_b_into_list_a_bit_for_bit(dim):
 
 
 # ------------------------------------------------------------------------------------------------ nrx_rows_to_dense
-@pytest.mark.parametrize("dim,mis", [(d, False) for d in (1, 6, 16, 17, 32, 320)] + [(16, True)])
-def test_rows_to_dense_stores_and_accumulates_the_lists_rows_bit_for_bit(dim, mis):
-    """Every key with a table of the call names its target, row 0 included (the dense gradient of the padding row is formed, and never applied)."""
+def _rows_to_dense_stores_and_accumulates(dim, n, mis):
+    """Every key with a table of the call names its target, row 0 included (the dense gradient of the padding row is formed, and never applied).
+    A long list (n >= 37) writes rows of all three tables; key_list's short ones write (table 1, row 1) and, from n = 4 on, (table 1, row 0)."""
     lib = _lib.load()
-    n = long_n(dim)
-    rng = np.random.default_rng([9, dim, int(mis)])
+    rng = np.random.default_rng([9, dim, int(mis)] + ([n] if n < 37 else []))
     rows = R.rows_for(n)
     keys, n_dev = R.key_list(n, rng, rows)
     vals = rng.standard_normal((n, dim)).astype(np.float32)
     t0 = [rng.standard_normal((rows, dim)).astype(np.float32) for _ in range(3)]
-    d_keys, d_vals, d_n = Guarded(keys), Guarded(vals, off=4 if mis else 0), Guarded(np.array([n_dev], dtype=np.int64))
-    targets = [(i,) + R.split_key(k) for i, k in enumerate(keys[:n_dev].tolist()) if k >= 0 and (k >> 40) < 3]
-    assert len(targets) >= n // 2 and any(r == 0 for _, _, r in targets) and len({(t, r) for _, t, r in targets}) == len(targets)
+    d_keys, d_vals = Guarded(keys), Guarded(vals, off=4 if mis else 0)
+    d_n = Guarded(np.array([n_dev], dtype=np.int64)) if n_dev is not None else None
+    live = keys if n_dev is None else keys[:n_dev]
+    targets = [(i,) + R.split_key(k) for i, k in enumerate(live.tolist()) if k >= 0 and (k >> 40) < 3]
+    assert len(targets) >= max(n // 2, 1) and len({(t, r) for _, t, r in targets}) == len(targets)
+    assert n < 4 or any(r == 0 for _, _, r in targets)
+    written = {t for _, t, _ in targets}
+    assert n < 37 or written == {0, 1, 2}
     for acc in (0, 1):
         d_t = [Guarded(x) for x in t0]
         want = [x.copy() for x in t0]
         for _ in range(1 + acc):
-            ops.check(lib.nrx_rows_to_dense(_ptrs([d.ptr for d in d_t]), 3, dim, d_keys.ptr, d_vals.ptr, n, d_n.ptr, acc, _stream()), "nrx_rows_to_dense")
+            ops.check(lib.nrx_rows_to_dense(_ptrs([d.ptr for d in d_t]), 3, dim, d_keys.ptr, d_vals.ptr, n, d_n.ptr if d_n is not None else None, acc,
+                                            _stream()), "nrx_rows_to_dense")
             for i, t, r in targets:
                 want[t][r] = want[t][r] + vals[i] if acc else vals[i]          # numpy's fp32 addition
         torch.cuda.synchronize()
         for t in range(3):
             assert _same(d_t[t].get(), want[t]), (t, "accumulate" if acc else "store")
-            assert not _same(want[t], t0[t])
-        hid_t, hid_r = R.split_key(keys[-1])                                     # the entry past the count left its target alone
-        assert _same(d_t[hid_t].get()[hid_r], t0[hid_t][hid_r])
-        assert all(d.intact() for d in d_t + [d_keys, d_vals, d_n]) and _same(d_keys.get(), keys) and _same(d_vals.get(), vals)
+            assert _same(want[t], t0[t]) == (t not in written)
+        if n_dev is not None:
+            hid_t, hid_r = R.split_key(keys[-1])                                 # the entry past the count left its target alone
+            assert _same(d_t[hid_t].get()[hid_r], t0[hid_t][hid_r])
+        assert all(d.intact() for d in d_t + [d_keys, d_vals] + ([d_n] if d_n is not None else []))
+        assert _same(d_keys.get(), keys) and _same(d_vals.get(), vals)
+
+
+@pytest.mark.parametrize("dim,mis", [(d, False) for d in (1, 6, 16, 17, 32, 320)] + [(16, True)])
+def test_rows_to_dense_stores_and_accumulates_the_lists_rows_bit_for_bit(dim, mis):
+    _rows_to_dense_stores_and_accumulates(dim, long_n(dim), mis)
+
+
+@pytest.mark.parametrize("n", [1, 3, 4, 5])
+@pytest.mark.parametrize("dim", [6, 16])
+def test_rows_to_dense_on_short_lists(dim, n):
+    """A partial group of four entries in both forms; at n = 4 and 5 one of the keys names row 0, which this kernel -- unlike the optimizers -- writes."""
+    _rows_to_dense_stores_and_accumulates(dim, n, False)

@@ -1081,6 +1081,35 @@ NRX_API int nrx_din_pool_bwd(const void* table, int64_t rows, int32_t dim, int32
                      float scale, const float* out, int64_t out_ld, const float* lse, const float* g_out, int64_t g_out_ld, float* g_query,
                      int64_t g_query_ld, float* g_rows, void* stream);
 
+/* ---- pairwise dot-product interaction (the product layer of the inner-product PNN, the interaction op of DLRM) ------------------
+ * x: fp32 [batch, ld].  Field f of sample b is e_f = x[b * ld + field_off[f] .. + dim); the fields need not be adjacent or ordered, must not
+ * overlap, and every field row is 16-byte aligned: x aligned, ld % 4 == 0, field_off[f] % 4 == 0.  field_off is a HOST array of n_fields
+ * entries: the offsets travel by value in the kernel arguments (no copy to the device: the call is capturable).
+ *   forward : z[b * z_ld + i (i - 1) / 2 + j] = dot(e_i, e_j) for 0 <= j < i < n_fields: P = F (F - 1) / 2 columns in the order of
+ *             tril_indices(F, F, -1).  flags bit 0 (NRX_DOT_SELF) includes the diagonal: P = F (F + 1) / 2, index i (i + 1) / 2 + j, j <= i.
+ *             dot(u, v), with H = dim / 2:  acc = 0;  for s = 0 .. H - 1 { acc = fmaf(u[s], v[s], acc);  acc = fmaf(u[H + s], v[H + s], acc); }
+ *             -- one fp32 chain, every product rounded once into the sum, the same chain for every (i, j) and every n_fields.
+ *   backward: g_e_f[c] = sum_j S[f][j] e_j[c] with S = G + G^T, G the (strict) lower-triangular matrix of g_z -- with NRX_DOT_SELF the
+ *             diagonal counts twice: S[f][f] = 2 g_z[f, f] -- as one chain in ascending j:
+ *             acc = 0;  for j = 0 .. F - 1 { acc = fmaf(S[f][j], e_j[c], acc); }   (S[f][f] = 0 without NRX_DOT_SELF takes its turn like any
+ *             other term; an odd F appends one term fmaf(0, 0, acc): the matrix instruction takes j in pairs.  Neither changes anything but
+ *             the sign of a zero.)   g_x[b * gx_ld + field_off[f] + c] = (accumulate ? g_x[...] + acc : acc).
+ * z / g_z need only 4-byte alignment and z_ld / gz_ld >= P.  z may be a column range of the buffer x lives in (z = x + width, z_ld = ld: the
+ * in-place cat form), and g_z one of the buffer of g_x: every read of a sample's fields (of its g_z row) completes before its z (its g_x) is
+ * stored.  z must not overlap any field, g_z no field's gradient (checked when they are such column ranges).  Bytes outside the result are
+ * never written: the columns of a z row from P on, the columns of a g_x row outside every field.
+ * One wave owns one sample: no atomics, no workspace, no allocation, copy or synchronisation.  The same bits run to run, and a sample's
+ * result does not depend on batch or on its place in it.
+ * n_fields in 2..64, dim a multiple of 4 in 4..64: anything else of valid form is NRX_ERR_UNSUPPORTED.  Null or misaligned pointers, strides
+ * below what they must hold (ld < dim or % 4 != 0, z_ld / gz_ld < P, gx_ld below a field's end), overlapping or out-of-row fields
+ * (field_off[f] + dim > ld), undefined flag bits, accumulate not 0 / 1, n_fields < 1, dim < 1: NRX_ERR_BAD_ARG before any launch, with
+ * nrx_last_error() naming the argument.  batch == 0: NRX_OK, nothing launched. */
+#define NRX_DOT_SELF 1
+NRX_API int nrx_dot_interact_fwd(const float* x, int64_t ld, const int32_t* field_off /* HOST, n_fields */, int32_t n_fields, int32_t dim,
+                     int64_t batch, int32_t flags, float* z, int64_t z_ld, void* stream);
+NRX_API int nrx_dot_interact_bwd(const float* x, int64_t ld, const int32_t* field_off /* HOST, n_fields */, int32_t n_fields, int32_t dim,
+                     int64_t batch, int32_t flags, const float* g_z, int64_t gz_ld, float* g_x, int64_t gx_ld, int32_t accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,7 @@ NRX_FEAT_MANY_PER_ROW = 4
 NRX_FEAT_TABLE_BF16 = 8           # the forward's table is bf16 [rows, dim]
 NRX_ADAGRAD_ROWWISE = 1           # nrx_sparse_adagrad_step flags
 NRX_ADAGRAD_TABLE_BF16 = 2
+NRX_DOT_SELF = 1                   # nrx_dot_interact_fwd / _bwd flags
 
 
 class NrxFeature(C.Structure):
@@ -214,6 +215,8 @@ SIGNATURES = {
     "nrx_attn_bwd": (C.c_int, [_p, _i64, _i64, _i32, _i32, _i32, C.c_float, _p, _p, _i64, _p, _p, _i64, _p, _i64, _p]),
     "nrx_din_pool_fwd": (C.c_int, [_p, _i64, _i32, _i32, _p, _i32, _p, _p, _i64, _i64, _i32, C.c_float, _p, _i64, _p, _p, _p]),
     "nrx_din_pool_bwd": (C.c_int, [_p, _i64, _i32, _i32, _p, _i32, _p, _p, _i64, _i64, _i32, C.c_float, _p, _i64, _p, _p, _i64, _p, _i64, _p, _p]),
+    "nrx_dot_interact_fwd": (C.c_int, [_p, _i64, C.POINTER(_i32), _i32, _i32, _i64, _i32, _p, _i64, _p]),
+    "nrx_dot_interact_bwd": (C.c_int, [_p, _i64, C.POINTER(_i32), _i32, _i32, _i64, _i32, _p, _i64, _p, _i64, _i32, _p]),
     "nrx_rep_pack": (C.c_int, [C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_i64), C.POINTER(_i32), _i32, C.POINTER(_i64),
                                C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32), _i32, _i32, _i64, _i64, _p, _p]),
     "nrx_rep_ordered_sum": (C.c_int, [_p, _i32, _i64, _i64, _p, _p]),

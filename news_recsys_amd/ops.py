@@ -13,6 +13,7 @@ Operator                          replaces (reference file:line)
   dcn_v2                           DCNv2Layer / DCNv2Net                dcn/dcn_arch.py:33-50,73-91
   bucketize_by_owner, gather_rows_segmented, mask_lengths   (new: row-sharded tables)
   din_pool                         (new: target attention over the click history)
+  dot_interaction / dot_interaction_cat_   (new: pairwise dot-product interaction of PNN / DLRM)
   itemcf_similarity / itemcf_recall  compute_item_similarity / recall_top_k_items  recall/ItemCF/itemCF_base.py:18-58
 """
 from __future__ import annotations
@@ -3187,6 +3188,175 @@ def din_pool_math(table: Optional[torch.Tensor], ids: Optional[torch.Tensor], qu
         lse = torch.where(some, m + torch.log(torch.where(some, den, torch.ones_like(den))), torch.full_like(den, float("-inf")))
         return out, lse.squeeze(1).detach()
     return out
+
+
+# ------------------------------------------------------------------------------- pairwise dot-product interaction (csrc/nrx_dot_interact.hip)
+DOT_INTERACT_MAX_FIELDS = 64
+DOT_INTERACT_MAX_DIM = 64
+dot_interaction_calls = 0        # forward launches of nrx_dot_interact_fwd so far (tests assert the model took the fused path)
+_dot_offsets = {}                # field offsets -> the host int32 array the entry points take
+
+
+def dot_interaction_supported(n_fields: int, dim: int) -> bool:
+    """The shapes nrx_dot_interact_fwd / _bwd take (anything else is NRX_ERR_UNSUPPORTED there)."""
+    return 2 <= n_fields <= DOT_INTERACT_MAX_FIELDS and 4 <= dim <= DOT_INTERACT_MAX_DIM and dim % 4 == 0
+
+
+def dot_interaction_pairs(n_fields: int, self_interaction: bool = False) -> int:
+    """P: the number of pair columns of n_fields fields."""
+    return n_fields * (n_fields + 1) // 2 if self_interaction else n_fields * (n_fields - 1) // 2
+
+
+def _dot_fields(field_off, dim: int, what: str) -> Tuple[int, ...]:
+    """field_off as a tuple of column offsets: a sequence of ints, or an int n_fields meaning adjacent fields from column 0."""
+    if isinstance(field_off, (int, np.integer)) and not isinstance(field_off, bool):
+        offs = tuple(range(0, int(field_off) * int(dim), int(dim)))
+    else:
+        offs = tuple(int(o) for o in field_off)
+    if not offs:
+        raise ValueError(f"{what}: field_off names no field")
+    return offs
+
+
+def _dot_off_array(offs: Tuple[int, ...]):
+    arr = _dot_offsets.get(offs)
+    if arr is None:
+        if len(_dot_offsets) > 256:
+            _dot_offsets.clear()
+        arr = _dot_offsets[offs] = (C.c_int32 * len(offs))(*offs)
+    return arr
+
+
+def _dot_check_shape(offs, dim: int, what: str) -> None:
+    if not dot_interaction_supported(len(offs), dim):
+        raise _lib.NrxError(f"{what}: unsupported shape (n_fields {len(offs)}, dim {dim}): n_fields 2..{DOT_INTERACT_MAX_FIELDS}, dim % 4 == 0 in "
+                            f"4..{DOT_INTERACT_MAX_DIM}")
+
+
+class _DotInteractFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, offs, dim, flags, ld):
+        global dot_interaction_calls
+        lib = _lib.load()
+        B = x.shape[0]
+        z = torch.empty((B, dot_interaction_pairs(len(offs), bool(flags))), dtype=torch.float32, device=x.device)
+        check(lib.nrx_dot_interact_fwd(x.data_ptr(), ld, _dot_off_array(offs), len(offs), dim, B, flags, z.data_ptr(), z.shape[1], _stream_ptr(x)),
+              "nrx_dot_interact_fwd")
+        dot_interaction_calls += 1
+        ctx.save_for_backward(x)
+        ctx.cfg = (offs, dim, flags, ld)
+        return z
+
+    @staticmethod
+    def backward(ctx, g_z):
+        lib = _lib.load()
+        x, = ctx.saved_tensors
+        offs, dim, flags, ld = ctx.cfg
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        B, W = x.shape
+        g = _f32c(g_z if g_z.dtype == torch.float32 else g_z.float(), "dot_interaction: grad")
+        # the columns of x outside every field take no part: their gradient is 0 (the kernel writes the field columns only)
+        covered = len(offs) * dim == W
+        g_x = torch.empty((B, W), dtype=torch.float32, device=x.device) if covered else torch.zeros((B, W), dtype=torch.float32, device=x.device)
+        check(lib.nrx_dot_interact_bwd(x.data_ptr(), ld, _dot_off_array(offs), len(offs), dim, B, flags, g.data_ptr(), g.shape[1], g_x.data_ptr(), W, 0,
+                                       _stream_ptr(x)), "nrx_dot_interact_bwd")
+        return g_x, None, None, None, None
+
+
+def dot_interaction(x: torch.Tensor, field_off, dim: int, self_interaction: bool = False) -> torch.Tensor:
+    """Pairwise dot-product interaction (the product layer of the inner-product PNN, the interaction op of DLRM): x [B, W] fp32 on the GPU holds
+    the fields e_f = x[:, field_off[f] : field_off[f] + dim] -> z [B, P] with z[:, i (i - 1) / 2 + j] = <e_i, e_j> for j < i, the order of
+    torch.tril_indices(F, F, -1) (self_interaction: j <= i, the order of tril_indices(F, F, 0)).  field_off: a sequence of column offsets
+    (multiples of 4; the fields must not overlap) or an int n_fields meaning adjacent fields from column 0.  No [B, F, F] tensor, forward or
+    backward (nrx_dot_interact_fwd / _bwd: one wave owns one sample, the products run on the matrix cores in an order the header spells out).
+    n_fields 2..64, dim a multiple of 4 in 4..64 (dot_interaction_supported); anything else raises.  A row-strided view (unit column stride,
+    row stride % 4 == 0, 16-byte aligned) is read in place, anything else through one contiguous copy -- whose rows are padded to a multiple
+    of 4 floats when the width of x is none.  Differentiable in x; runs on the current stream with no host synchronisation
+    (graph-capturable); the same bits run to run and whatever the batch around a sample."""
+    dim = int(dim)
+    offs = _dot_fields(field_off, dim, "dot_interaction")
+    x = _rows16(x, "dot_interaction: x")
+    W = x.shape[1]
+    ld = x.stride(0) if x.shape[0] > 1 else W
+    if ld % 4 != 0:          # (a contiguous x whose width is no multiple of 4: the one copy, with the row stride the kernels need)
+        ld = W + (-W) % 4
+        x = torch.nn.functional.pad(x, (0, ld - W))[:, :W]
+    if any(o < 0 or o + dim > x.shape[1] for o in offs):
+        raise ValueError(f"dot_interaction: a field of dim {dim} leaves the {x.shape[1]} columns of x (field_off {list(offs)})")
+    _dot_check_shape(offs, dim, "dot_interaction")
+    return _DotInteractFn.apply(x, offs, dim, _lib.NRX_DOT_SELF if self_interaction else 0, ld)
+
+
+class _DotInteractCatFn(torch.autograd.Function):
+    """In place: buf[:, :width] holds the concat (written by embed_apply with out_ld = buf.shape[1]); fills buf[:, width : width + P] with the
+    pair products, giving torch.cat([concat, z], dim=1) without the extra pass."""
+
+    @staticmethod
+    def forward(ctx, buf, width, offs, dim, flags):
+        global dot_interaction_calls
+        lib = _lib.load()
+        B, ld = buf.shape
+        check(lib.nrx_dot_interact_fwd(buf.data_ptr(), ld, _dot_off_array(offs), len(offs), dim, B, flags, buf.data_ptr() + 4 * width, ld,
+                                       _stream_ptr(buf)), "nrx_dot_interact_fwd")
+        dot_interaction_calls += 1
+        ctx.mark_dirty(buf)
+        ctx.save_for_backward(buf)
+        ctx.cfg = (width, offs, dim, flags)
+        return buf
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        buf, = ctx.saved_tensors
+        width, offs, dim, flags = ctx.cfg
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        B, ld = buf.shape
+        g = _f32c(g if g.dtype == torch.float32 else g.float(), "dot_interaction_cat_: grad")
+        # the gradient of the buffer that came in: the upstream gradient of the concat columns (copied: autograd's gradient is not ours to
+        # update) PLUS the interaction's, added onto the field columns in the launch itself; the columns from `width` on were never read: 0
+        gbuf = torch.empty_like(g)
+        gbuf[:, :width].copy_(g[:, :width])
+        gbuf[:, width:].zero_()
+        check(lib.nrx_dot_interact_bwd(buf.data_ptr(), ld, _dot_off_array(offs), len(offs), dim, B, flags, g.data_ptr() + 4 * width, ld,
+                                       gbuf.data_ptr(), ld, 1, _stream_ptr(buf)), "nrx_dot_interact_bwd")
+        return gbuf, None, None, None, None
+
+
+def dot_interaction_cat_(buf: torch.Tensor, width: int, field_off, dim: int, self_interaction: bool = False) -> torch.Tensor:
+    """dot_interaction in place, next to its input: buf [B, ld] fp32, contiguous, holds the concat in columns [0, width) -- embed_apply(...,
+    out_ld=ld) writes such a buffer -- and the fields at the column offsets field_off inside it; the P pair products go into columns
+    [width, width + P) and buf is returned: torch.cat([concat, z], dim=1) without the pass.  ld >= width + P and ld % 4 == 0 (so
+    ld = width + P rounded up to 4); the pad columns [width + P, ld) are NEVER WRITTEN and must not be read: slice them off as a view.  The
+    backward adds the interaction's gradient onto the upstream gradient of the concat columns in its one launch."""
+    _dev(buf, "dot_interaction_cat_: buf")
+    if buf.dtype != torch.float32:
+        raise TypeError(f"dot_interaction_cat_: buf must be float32, got {buf.dtype}")
+    dim, width = int(dim), int(width)
+    offs = _dot_fields(field_off, dim, "dot_interaction_cat_")
+    flags = _lib.NRX_DOT_SELF if self_interaction else 0
+    P = dot_interaction_pairs(len(offs), self_interaction)
+    if buf.dim() != 2 or not buf.is_contiguous() or buf.shape[1] % 4 != 0 or buf.data_ptr() % 16 != 0:
+        raise ValueError("dot_interaction_cat_: buf must be a contiguous, 16-byte aligned [B, ld] tensor with ld % 4 == 0")
+    if width < 0 or width + P > buf.shape[1]:
+        raise ValueError(f"dot_interaction_cat_: buf has {buf.shape[1]} columns, width {width} + {P} pair columns do not fit")
+    if any(o < 0 or o + dim > width for o in offs):
+        raise ValueError(f"dot_interaction_cat_: a field of dim {dim} leaves the concat columns [0, {width}) (field_off {list(offs)})")
+    _dot_check_shape(offs, dim, "dot_interaction_cat_")
+    return _DotInteractCatFn.apply(buf, width, offs, dim, flags)
+
+
+def dot_interaction_math(x: torch.Tensor, field_off, dim: int, self_interaction: bool = False) -> torch.Tensor:
+    """dot_interaction's definition in plain torch, on any device and in the dtype of x (the fallback and the yardstick): the fields stacked
+    to [B, F, D], bmm with their transpose, the lower triangle picked in tril_indices order.  Differentiable by autograd."""
+    dim = int(dim)
+    offs = _dot_fields(field_off, dim, "dot_interaction_math")
+    e = torch.stack([x[:, o:o + dim] for o in offs], dim=1)
+    zz = torch.bmm(e, e.transpose(1, 2))
+    F = len(offs)
+    i, j = torch.tril_indices(F, F, 0 if self_interaction else -1, device=x.device)
+    return zz[:, i, j]
 
 
 # ------------------------------------------------------------------------------- ItemCF recall (csrc/nrx_itemcf.hip, DESIGN 7f)

@@ -1066,6 +1066,9 @@ def shard_model_(model, rank: int, world: int, group=None, backend=None):
     if getattr(model, "din_cfg", None) is not None:
         raise NotImplementedError("shard_model_: a model with din_cfg (sort/din: target-attention pooling of the history) is not supported -- the "
                                   "exchange engine's routing does not know that operator")
+    if getattr(model, "pnn_cfg", None) is not None:
+        raise NotImplementedError("shard_model_: a model with pnn_cfg (sort/pnn: pairwise dot-product interaction) is not supported -- the "
+                                  "bound step does not know that operator")
     if any(e.weight.dtype is torch.bfloat16 for e in model.embedding_tables.values()):
         raise NotImplementedError("shard_model_: bf16 embedding tables are not supported here -- its backward forms dense shard gradients, which "
                                   "bf16 tables never have; the bound step trains them: shard_step.shard_model_step_(..., bf16_tables=True)")

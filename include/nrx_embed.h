@@ -1110,6 +1110,46 @@ NRX_API int nrx_dot_interact_fwd(const float* x, int64_t ld, const int32_t* fiel
 NRX_API int nrx_dot_interact_bwd(const float* x, int64_t ld, const int32_t* field_off /* HOST, n_fields */, int32_t n_fields, int32_t dim,
                      int64_t batch, int32_t flags, const float* g_z, int64_t gz_ld, float* g_x, int64_t gx_ld, int32_t accumulate, void* stream);
 
+/* ---- Compressed Interaction Network (the explicit vector-wise interaction of xDeepFM, Lian et al. KDD 2018 eq. 6-8) -------------
+ * One layer per call.  X0[b, j, d] = x0[b * x0_ld + field_off[j] + d] (m fields of a concat row, read in place: the nrx_dot_interact_fwd
+ * convention -- 16-byte aligned, not overlapping, neither adjacent nor ordered; field_off is a HOST array).  Xp = X^{k-1}: xprev [batch, Hp * dim]
+ * with row stride xprev_ld, Xp[b, i, d] = xprev[b * xprev_ld + i * dim + d]; xprev == NULL is layer 1: Xp = X0, and Hp must equal m.
+ * W: [H, Hp, m] contiguous.  All fp32.
+ *   forward : xk[b * xk_ld + h * dim + d] = sum_{i < Hp, j < m} W[h, i, j] Xp[b, i, d] X0[b, j, d] as ONE fp32 chain over k = i * m + j ascending:
+ *                 acc = 0;  for k = 0 .. Hp m - 1 { acc = fmaf(fl(Xp[b, i, d] * X0[b, j, d]), W[h, i, j], acc); }
+ *             (fl: the product rounded to fp32 first; an odd Hp m appends one term fmaf(0, 0, acc): the matrix instruction takes k in pairs).
+ *             xk may be NULL (the last layer needs p only).
+ *             p[b * p_ld + h] = sum_d xk[b, h, d]:  s = 0;  for d = 0 .. dim - 1 { s = s + xk[b, h, d]; }  (fp32, ascending d).  p points at this
+ *             layer's first column of a [batch, p_ld] buffer: the layers' pooled outputs land side by side.
+ *   backward: G[b, h, d] = g_xk ? fl(g_p[b * gp_ld + h] + g_xk[b * gxk_ld + h * dim + d]) : g_p[b * gp_ld + h]    (g_xk may be NULL)
+ *             A[b, j, d] = chain from 0 over k = h * Hp + i ascending of fmaf(fl(G[b, h, d] * Xp[b, i, d]), W[h, i, j], acc)   (odd H Hp: + fmaf(0, 0, .))
+ *             C[b, i, d] = chain from 0 over k = h * m + j ascending of fmaf(fl(G[b, h, d] * X0[b, j, d]), W[h, i, j], acc)    (odd H m:  + fmaf(0, 0, .))
+ *             g_x0[b * gx0_ld + field_off[j] + d] = accumulate_x0 ? fl(g_x0[..] + A) : A;   g_xprev[b * gxprev_ld + i * dim + d] = C.
+ *             Layer 1 (xprev == NULL; g_xprev must be NULL too): the second term lands on X0 as well: g_x0[.. field_off[i] + d] = fl(g_x0[..] + C)
+ *             after the first.
+ *             g_W[h, i, j] = sum_{b, d} G Xp X0 in SLICES of nrx_cin_wgrad_slice(dim) samples (a function of dim alone): slice s covers the
+ *             samples [s SL, min((s + 1) SL, batch)), its partial is one chain from 0 over (b ascending, d ascending) of
+ *             fmaf(G[b, h, d], fl(Xp[b, i, d] * X0[b, j, d]), acc); g_W = ((part_0 + part_1) + part_2) + ... in slice order (a second launch; no
+ *             atomics).  workspace: nrx_cin_layer_bwd_workspace(batch, m, Hp, H, dim) device bytes (the partials), 4-byte aligned.
+ * xk, p, g_xprev and g_x0 are functions of the one sample: their bits depend neither on batch, nor on the sample's place in it, nor on the grid;
+ * g_W is the same bits run to run.  One owner per output element; nothing outside the stated outputs is written (pad columns, the columns of a g_x0
+ * row outside every field, the other columns of the p buffer).  No allocation, copy or synchronisation: capturable.
+ * xk, xprev, g_xk, g_xprev: 16-byte aligned, row strides % 4 == 0 and >= the row; p, g_p: 4-byte aligned, p_ld / gp_ld >= H; gx0_ld % 4 == 0 and
+ * holds every field.  nrx_cin_supported(m, Hp, H, dim): 1 for m in 2..64, Hp and H in 1..64, dim a multiple of 4 in 4..64, else 0 -- outside it the
+ * launch entry points return NRX_ERR_UNSUPPORTED with nothing enqueued.  Null or misaligned pointers, strides below what they must hold,
+ * overlapping or out-of-row fields, xprev == NULL with Hp != m, g_xprev null-ness differing from xprev's, accumulate_x0 not 0 / 1, a count < 1:
+ * NRX_ERR_BAD_ARG before any launch, nrx_last_error() naming the argument.  batch == 0: NRX_OK, nothing launched. */
+NRX_API int nrx_cin_supported(int32_t m, int32_t Hp, int32_t H, int32_t dim);
+NRX_API int64_t nrx_cin_wgrad_slice(int32_t dim);
+NRX_API int64_t nrx_cin_layer_bwd_workspace(int64_t batch, int32_t m, int32_t Hp, int32_t H, int32_t dim);
+NRX_API int nrx_cin_layer_fwd(const float* x0, int64_t x0_ld, const int32_t* field_off /* HOST, m */, int32_t m, int32_t dim, const float* xprev,
+                     int64_t xprev_ld, int32_t Hp, const float* W, int32_t H, int64_t batch, float* xk, int64_t xk_ld, float* p, int64_t p_ld,
+                     void* stream);
+NRX_API int nrx_cin_layer_bwd(const float* x0, int64_t x0_ld, const int32_t* field_off /* HOST, m */, int32_t m, int32_t dim, const float* xprev,
+                     int64_t xprev_ld, int32_t Hp, const float* W, int32_t H, int64_t batch, const float* g_p, int64_t gp_ld, const float* g_xk,
+                     int64_t gxk_ld, float* g_xprev, int64_t gxprev_ld, float* g_x0, int64_t gx0_ld, int32_t accumulate_x0, float* g_W,
+                     void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ Operator                          replaces (reference file:line)
   bucketize_by_owner, gather_rows_segmented, mask_lengths   (new: row-sharded tables)
   din_pool                         (new: target attention over the click history)
   dot_interaction / dot_interaction_cat_   (new: pairwise dot-product interaction of PNN / DLRM)
+  cin / cin_math                   (new: Compressed Interaction Network of xDeepFM)
   itemcf_similarity / itemcf_recall  compute_item_similarity / recall_top_k_items  recall/ItemCF/itemCF_base.py:18-58
 """
 from __future__ import annotations
@@ -3357,6 +3358,132 @@ def dot_interaction_math(x: torch.Tensor, field_off, dim: int, self_interaction:
     F = len(offs)
     i, j = torch.tril_indices(F, F, 0 if self_interaction else -1, device=x.device)
     return zz[:, i, j]
+
+
+# ------------------------------------------------------------------------------- Compressed Interaction Network (csrc/nrx_cin.hip)
+CIN_MAX = 64                     # m, Hp, H
+CIN_MAX_DIM = 64
+cin_calls = 0                    # forward launches of nrx_cin_layer_fwd so far: one per layer (tests assert the model took the fused path)
+
+
+def cin_supported(m: int, Hp: int, H: int, dim: int) -> bool:
+    """The layer shapes nrx_cin_layer_fwd / _bwd take (nrx_cin_supported; anything else is NRX_ERR_UNSUPPORTED there)."""
+    return 2 <= m <= CIN_MAX and 1 <= Hp <= CIN_MAX and 1 <= H <= CIN_MAX and 4 <= dim <= CIN_MAX_DIM and dim % 4 == 0
+
+
+def cin_out_width(layer_sizes) -> int:
+    """Columns of cin's result: the layers' pooled feature maps side by side."""
+    return int(sum(int(h) for h in layer_sizes))
+
+
+def _cin_layers(m: int, weights, what: str):
+    """[(Hp, H)] per layer; checks that the weights chain: W_k [H_k, H_{k-1}, m], H_0 = m."""
+    if len(weights) == 0:
+        raise ValueError(f"{what}: no layer weights")
+    shapes, Hp = [], m
+    for k, W in enumerate(weights):
+        if W.dim() != 3 or W.shape[1] != Hp or W.shape[2] != m or W.shape[0] < 1:
+            raise ValueError(f"{what}: weights[{k}] must be [H_{k + 1}, {Hp}, {m}] (H_k, H_(k-1), m), got {tuple(W.shape)}")
+        shapes.append((Hp, int(W.shape[0])))
+        Hp = int(W.shape[0])
+    return shapes
+
+
+def cin_math(x: torch.Tensor, field_off, dim: int, weights) -> torch.Tensor:
+    """cin's definition in plain torch, on any device and in the dtype of x (the fallback, the float64 restatement and the yardstick): the
+    outer product einsum('bid,bjd->bijd') of X^{k-1} and X^0, the 1x1 convolution with W_k, sum pooling over d; the layers' pooled maps side
+    by side.  Differentiable by autograd.  Materialises [B, Hp, m, D] per layer."""
+    dim = int(dim)
+    offs = _dot_fields(field_off, dim, "cin_math")
+    _cin_layers(len(offs), weights, "cin_math")
+    x0 = torch.stack([x[:, o:o + dim] for o in offs], dim=1)
+    xp, pooled = x0, []
+    for W in weights:
+        z = torch.einsum("bid,bjd->bijd", xp, x0)
+        xp = torch.einsum("hij,bijd->bhd", W.to(x.dtype), z)
+        pooled.append(xp.sum(-1))
+    return torch.cat(pooled, dim=1)
+
+
+class _CinFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, offs, dim, ld, *weights):
+        global cin_calls
+        lib = _lib.load()
+        B, m = x.shape[0], len(offs)
+        shapes = _cin_layers(m, weights, "cin")
+        ws = [_f32c(W.detach(), "cin: weights") for W in weights]
+        out = torch.empty((B, sum(H for _, H in shapes)), dtype=torch.float32, device=x.device)
+        off_arr, st = _dot_off_array(offs), _stream_ptr(x)
+        xs, xprev, col = [], None, 0
+        for k, ((Hp, H), W) in enumerate(zip(shapes, ws)):
+            xk = torch.empty((B, H * dim), dtype=torch.float32, device=x.device) if k + 1 < len(ws) else None       # (the last layer needs p only)
+            check(lib.nrx_cin_layer_fwd(x.data_ptr(), ld, off_arr, m, dim, _ptr(xprev), Hp * dim, Hp, W.data_ptr(), H, B, _ptr(xk), H * dim,
+                                        out.data_ptr() + 4 * col, out.shape[1], st), "nrx_cin_layer_fwd")
+            cin_calls += 1
+            if xk is not None:
+                xs.append(xk)
+            xprev, col = xk, col + H
+        ctx.save_for_backward(x, *ws, *xs)
+        ctx.cfg = (offs, dim, ld, shapes)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        lib = _lib.load()
+        offs, dim, ld, shapes = ctx.cfg
+        L = len(shapes)
+        x, ws, xs = ctx.saved_tensors[0], ctx.saved_tensors[1:1 + L], ctx.saved_tensors[1 + L:]
+        B, Wd = x.shape
+        m = len(offs)
+        g = _f32c(g_out if g_out.dtype == torch.float32 else g_out.float(), "cin: grad")
+        gld = Wd + (-Wd) % 4
+        # the columns of x outside every field take no part: their gradient is 0 (the kernels write the field columns only)
+        covered = m * dim == gld
+        g_x = torch.empty((B, gld), dtype=torch.float32, device=x.device) if covered else torch.zeros((B, gld), dtype=torch.float32, device=x.device)
+        wsp = torch.empty((max(lib.nrx_cin_layer_bwd_workspace(B, m, Hp, H, dim) for Hp, H in shapes) + 3) // 4, dtype=torch.float32, device=x.device)
+        off_arr, st = _dot_off_array(offs), _stream_ptr(x)
+        g_ws = [None] * L
+        g_xk, col = None, g.shape[1]
+        for k in range(L - 1, -1, -1):
+            Hp, H = shapes[k]
+            col -= H
+            xprev = xs[k - 1] if k > 0 else None
+            g_xprev = torch.empty((B, Hp * dim), dtype=torch.float32, device=x.device) if k > 0 else None
+            g_ws[k] = torch.empty_like(ws[k])
+            check(lib.nrx_cin_layer_bwd(x.data_ptr(), ld, off_arr, m, dim, _ptr(xprev), Hp * dim, Hp, ws[k].data_ptr(), H, B, g.data_ptr() + 4 * col,
+                                        g.shape[1], _ptr(g_xk), H * dim, _ptr(g_xprev), Hp * dim, g_x.data_ptr(), gld, 0 if k == L - 1 else 1,
+                                        g_ws[k].data_ptr(), wsp.data_ptr(), st), "nrx_cin_layer_bwd")
+            g_xk = g_xprev
+        return (g_x if gld == Wd else g_x[:, :Wd], None, None, None, *g_ws)
+
+
+def cin(x: torch.Tensor, field_off, dim: int, weights) -> torch.Tensor:
+    """Compressed Interaction Network (xDeepFM, Lian et al. KDD 2018 eq. 6-8): x [B, W] fp32 holds the m fields X^0[:, j, :] =
+    x[:, field_off[j] : field_off[j] + dim]; weights[k] is W_k [H_k, H_{k-1}, m] (H_0 = m) ->  [B, sum H_k]: layer k forms
+    X^k[b, h, d] = sum_{i, j} W_k[h, i, j] X^{k-1}[b, i, d] X^0[b, j, d] and contributes its sum over d.  No [B, Hp, m, D] tensor, forward or
+    backward: each layer is a GEMM on the matrix cores whose A operand is multiplied out in registers (nrx_cin_layer_fwd / _bwd; the header
+    spells out every fp32 chain).  The backward keeps only the X^k of the non-final layers.  field_off as dot_interaction's.  On the GPU with a
+    supported shape (cin_supported for every layer) the fused kernels run, on the current stream with no host synchronisation
+    (graph-capturable; the same bits run to run); CPU tensors and unsupported shapes take cin_math.  A row-strided view (unit column stride,
+    row stride % 4 == 0, 16-byte aligned) is read in place, anything else through one contiguous copy."""
+    dim = int(dim)
+    offs = _dot_fields(field_off, dim, "cin")
+    weights = list(weights)
+    shapes = _cin_layers(len(offs), weights, "cin")
+    if x.dim() != 2:
+        raise ValueError(f"cin: expected x [batch, width], got {tuple(x.shape)}")
+    if any(o < 0 or o + dim > x.shape[1] for o in offs):
+        raise ValueError(f"cin: a field of dim {dim} leaves the {x.shape[1]} columns of x (field_off {list(offs)})")
+    if not x.is_cuda or x.dtype != torch.float32 or any(o % 4 != 0 for o in offs) or not all(cin_supported(len(offs), Hp, H, dim) for Hp, H in shapes):
+        return cin_math(x, offs, dim, weights)
+    x = _rows16(x, "cin: x")
+    W = x.shape[1]
+    ld = x.stride(0) if x.shape[0] > 1 else W
+    if ld % 4 != 0:          # (a contiguous x whose width is no multiple of 4: the one copy, with the row stride the kernels need)
+        ld = W + (-W) % 4
+        x = torch.nn.functional.pad(x, (0, ld - W))[:, :W]
+    return _CinFn.apply(x, offs, dim, ld, *weights)
 
 
 # ------------------------------------------------------------------------------- ItemCF recall (csrc/nrx_itemcf.hip, DESIGN 7f)

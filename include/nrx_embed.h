@@ -1150,6 +1150,51 @@ NRX_API int nrx_cin_layer_bwd(const float* x0, int64_t x0_ld, const int32_t* fie
                      int64_t gxk_ld, float* g_xprev, int64_t gxprev_ld, float* g_x0, int64_t gx0_ld, int32_t accumulate_x0, float* g_W,
                      void* workspace, void* stream);
 
+/* ---- attentional pooling of pairwise field interactions (Attentional Factorization Machine, Xiao et al. IJCAI 2017) -------------
+ * x: fp32 [batch, ld]; field f of sample b is e_f = x[b * ld + field_off[f] .. + dim) (the nrx_dot_interact_fwd convention: 16-byte aligned,
+ * not overlapping, neither adjacent nor ordered; field_off is a HOST array).  Pairs p = (i, j), 0 <= j < i < F, p = i (i - 1) / 2 + j (the order
+ * of tril_indices(F, F, -1)), P = F (F - 1) / 2.  W1 [A, dim], b1 [A], w2 [A]: fp32, contiguous.  h_p[d] = fl(e_i[d] * e_j[d]) (rounded once).
+ *   forward : z_p,t = chain from b1[t] over d = 0 .. dim - 1 ascending:  acc = b1[t];  for d { acc = fmaf(W1[t, d], h_p[d], acc); }
+ *             (v_mfma_f32_32x32x2_f32 takes d in pairs; dim is even; the rounded product is one operand).
+ *             a_p = fl(s_0 + s_1), s_k the chain from 0 over the t with ((t >> 2) & 1) == k ascending (t < 64; w2[t] = 0, z = 0 from A on):
+ *                 s_k = fmaf(w2[t], max(z_p,t, 0), s_k)       -- the two halves of the matrix instruction's result layout.
+ *             m = max_p a_p;  E_p = expf(fl(a_p - m)) (the device library's expf, within 1 ulp -- not the fast exp2 form);
+ *             l = the sum of E_p: lane q of 64 adds p = q, q + 64, .. ascending from 0, then the 64 partials are added as a butterfly
+ *             (v = v + v[lane ^ 32], ^ 16, .. ^ 1);  alpha_p = fl(E_p / l);  lse[b] = fl(m + logf(l)).
+ *             out[b * out_ld + d] = ((g_0 + g_1) + ..) + g_{G-1}, G = 64 / dim (integer division), g_q the chain from 0 over p = q, q + G, ..
+ *             ascending of fmaf(alpha_p, h_p[d], g_q).
+ *   backward (from x, the parameters, out, lse and g_out alone; z, a, alpha recomputed; nothing of size batch * P exists):
+ *             alpha_p = expf(fl(a_p - lse[b]));  dalpha_p = fl(c_0 + c_1), c_k the chain from 0 over d = k, k + 2, .. of fmaf(g_out[d], h_p[d], c_k);
+ *             delta = chain from 0 over d ascending of fmaf(g_out[d], out[d], .);  da_p = fl(alpha_p * fl(dalpha_p - delta));
+ *             u_p,t = z_p,t > 0 ? fl(da_p * w2[t]) : 0;
+ *             g_h_p[d] = chain from fl(alpha_p * g_out[d]) over t in the order 0, 4, 1, 5, 2, 6, 3, 7, 8, 12, 9, 13, .. (t = (s & 3) + 8 (s >> 2) + 4 k,
+ *             s = 0 .. 15, k = 0, 1, then the same from 32 on; rows of 8 wholly past A are skipped) of fmaf(W1[t, d], u_p,t, .);
+ *             g_e_i[d] = chain from 0 over j = 0 .. 32 ceil(F / 32) - 1 ascending of (acc + fl(g_h_(i,j)[d] * e_j[d])), the term of j = i and of
+ *             j >= F being 0 ((i, j) with j > i is the pair (j, i): its values are recomputed, the same bits).
+ *             g_x[b * gx_ld + field_off[i] + d] = g_e_i[d]: the field columns only are written.
+ *             g_W1, g_b1, g_w2 in SLICES of nrx_afm_wgrad_slice(F, dim, A) samples (a function of the shape alone): slice s covers the samples
+ *             [s SL, min((s + 1) SL, batch)); over (b ascending, i ascending, j < i ascending in pairs (j, j + 1)):
+ *                 part_W1[t, d] = fmaf(u_(i,j),t, h_(i,j)[d], .) from 0;  part_b1[t] = fl(o_0 + o_1) and part_w2[t] = fl(r_0 + r_1), o_k / r_k the sums
+ *                 over the j of parity k: o_k = o_k + u_(i,j),t;  r_k = fmaf(da_(i,j), max(z_(i,j),t, 0), r_k)
+ *             (an odd count of j < i (within 32) appends one term of zeros).  g = ((part_0 + part_1) + part_2) + .. in slice order (a second
+ *             launch; no atomics).  workspace: nrx_afm_bwd_workspace(batch, F, dim, A) device bytes, 4-byte aligned.
+ * out, lse and g_x are functions of the one sample: their bits depend neither on batch, nor on the sample's place in it, nor on the grid; the
+ * parameter gradients are the same bits run to run.  One owner per output element, no float atomics; nothing outside the stated outputs is
+ * written (pad columns, the columns of a g_x row outside every field).  No allocation, copy or synchronisation: capturable.
+ * x: 16-byte aligned, ld % 4 == 0; every other pointer 4-byte aligned; out_ld, g_out_ld >= dim; gx_ld holds every field.
+ * nrx_afm_supported(F, dim, A): 1 for F in 2..64, dim a multiple of 4 in 4..64, A in 1..64, else 0 -- outside it the launch entry points
+ * return NRX_ERR_UNSUPPORTED with nothing enqueued.  Null or misaligned pointers, strides below what they must hold, overlapping or out-of-row
+ * fields, a count < 1: NRX_ERR_BAD_ARG before any launch, nrx_last_error() naming the argument.  batch == 0: NRX_OK, nothing launched. */
+NRX_API int nrx_afm_supported(int32_t n_fields, int32_t dim, int32_t A);
+NRX_API int64_t nrx_afm_wgrad_slice(int32_t n_fields, int32_t dim, int32_t A);
+NRX_API int64_t nrx_afm_bwd_workspace(int64_t batch, int32_t n_fields, int32_t dim, int32_t A);
+NRX_API int nrx_afm_fwd(const float* x, int64_t ld, const int32_t* field_off /* HOST, n_fields */, int32_t n_fields, int32_t dim, const float* W1,
+                     const float* b1, const float* w2, int32_t A, int64_t batch, float* out, int64_t out_ld, float* lse, void* stream);
+NRX_API int nrx_afm_bwd(const float* x, int64_t ld, const int32_t* field_off /* HOST, n_fields */, int32_t n_fields, int32_t dim, const float* W1,
+                     const float* b1, const float* w2, int32_t A, int64_t batch, const float* out, int64_t out_ld, const float* lse,
+                     const float* g_out, int64_t g_out_ld, float* g_x, int64_t gx_ld, float* g_W1, float* g_b1, float* g_w2, void* workspace,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

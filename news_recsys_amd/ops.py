@@ -15,6 +15,7 @@ Operator                          replaces (reference file:line)
   din_pool                         (new: target attention over the click history)
   dot_interaction / dot_interaction_cat_   (new: pairwise dot-product interaction of PNN / DLRM)
   cin / cin_math                   (new: Compressed Interaction Network of xDeepFM)
+  afm_pool / afm_pool_math         (new: attentional pooling of pairwise field interactions, AFM)
   itemcf_similarity / itemcf_recall  compute_item_similarity / recall_top_k_items  recall/ItemCF/itemCF_base.py:18-58
 """
 from __future__ import annotations
@@ -3484,6 +3485,104 @@ def cin(x: torch.Tensor, field_off, dim: int, weights) -> torch.Tensor:
         ld = W + (-W) % 4
         x = torch.nn.functional.pad(x, (0, ld - W))[:, :W]
     return _CinFn.apply(x, offs, dim, ld, *weights)
+
+
+# ------------------------------------------------------------------------------- attentional pooling of pair interactions (csrc/nrx_afm.hip)
+AFM_MAX = 64                     # F, dim, A
+afm_calls = 0                    # forward launches of nrx_afm_fwd so far (tests assert the model took the fused path)
+
+
+def afm_supported(n_fields: int, dim: int, A: int) -> bool:
+    """The shapes nrx_afm_fwd / _bwd take (nrx_afm_supported; anything else is NRX_ERR_UNSUPPORTED there)."""
+    return 2 <= n_fields <= AFM_MAX and 4 <= dim <= AFM_MAX and dim % 4 == 0 and 1 <= A <= AFM_MAX
+
+
+def _afm_params(dim: int, w1, b1, w2, what: str) -> int:
+    if w1.dim() != 2 or w1.shape[1] != dim or w1.shape[0] < 1:
+        raise ValueError(f"{what}: w1 must be [A, {dim}], got {tuple(w1.shape)}")
+    A = int(w1.shape[0])
+    if tuple(b1.shape) != (A,) or tuple(w2.shape) != (A,):
+        raise ValueError(f"{what}: b1 and w2 must be [{A}], got {tuple(b1.shape)} and {tuple(w2.shape)}")
+    return A
+
+
+def afm_pool_math(x: torch.Tensor, field_off, dim: int, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor) -> torch.Tensor:
+    """afm_pool's definition in plain torch, on any device and in the dtype of x (the fallback, the float64 restatement and the yardstick): the
+    pair products h [B, P, dim] in tril_indices(F, F, -1) order, a = relu(h w1^T + b1) w2, softmax over the pairs, the weighted sum of h.
+    Differentiable by autograd.  Materialises [B, P, dim] and [B, P, A]."""
+    dim = int(dim)
+    offs = _dot_fields(field_off, dim, "afm_pool_math")
+    _afm_params(dim, w1, b1, w2, "afm_pool_math")
+    e = torch.stack([x[:, o:o + dim] for o in offs], dim=1)
+    F = len(offs)
+    i, j = torch.tril_indices(F, F, -1, device=x.device)
+    h = e[:, i] * e[:, j]
+    a = torch.relu(h @ w1.to(x.dtype).t() + b1.to(x.dtype)) @ w2.to(x.dtype)
+    return (torch.softmax(a, dim=1).unsqueeze(-1) * h).sum(1)
+
+
+class _AfmFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, offs, dim, ld, w1, b1, w2):
+        global afm_calls
+        lib = _lib.load()
+        B, F, A = x.shape[0], len(offs), w1.shape[0]
+        ws = [_f32c(t.detach(), "afm_pool: parameters") for t in (w1, b1, w2)]
+        out = torch.empty((B, dim), dtype=torch.float32, device=x.device)
+        lse = torch.empty((B,), dtype=torch.float32, device=x.device)
+        check(lib.nrx_afm_fwd(x.data_ptr(), ld, _dot_off_array(offs), F, dim, ws[0].data_ptr(), ws[1].data_ptr(), ws[2].data_ptr(), A, B, out.data_ptr(),
+                              dim, lse.data_ptr(), _stream_ptr(x)), "nrx_afm_fwd")
+        afm_calls += 1
+        ctx.save_for_backward(x, *ws, out, lse)
+        ctx.cfg = (offs, dim, ld)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        lib = _lib.load()
+        offs, dim, ld = ctx.cfg
+        x, w1, b1, w2, out, lse = ctx.saved_tensors
+        B, Wd = x.shape
+        F, A = len(offs), w1.shape[0]
+        g = _f32c(g_out if g_out.dtype == torch.float32 else g_out.float(), "afm_pool: grad")
+        # the columns of x outside every field take no part: their gradient is 0 (the kernel writes the field columns only)
+        covered = F * dim == Wd
+        g_x = torch.empty((B, Wd), dtype=torch.float32, device=x.device) if covered else torch.zeros((B, Wd), dtype=torch.float32, device=x.device)
+        g_w1, g_b1, g_w2 = torch.empty_like(w1), torch.empty_like(b1), torch.empty_like(w2)
+        wsp = torch.empty((lib.nrx_afm_bwd_workspace(B, F, dim, A) + 3) // 4, dtype=torch.float32, device=x.device)
+        check(lib.nrx_afm_bwd(x.data_ptr(), ld, _dot_off_array(offs), F, dim, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), A, B, out.data_ptr(), dim,
+                              lse.data_ptr(), g.data_ptr(), g.shape[1], g_x.data_ptr(), Wd, g_w1.data_ptr(), g_b1.data_ptr(), g_w2.data_ptr(),
+                              wsp.data_ptr(), _stream_ptr(x)), "nrx_afm_bwd")
+        return g_x, None, None, None, g_w1, g_b1, g_w2
+
+
+def afm_pool(x: torch.Tensor, field_off, dim: int, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor) -> torch.Tensor:
+    """Attentional pooling of the pairwise field interactions (AFM, Xiao et al. IJCAI 2017): x [B, W] holds the F fields e_f =
+    x[:, field_off[f] : field_off[f] + dim]; every pair product h_p = e_i * e_j (j < i, tril_indices order) is scored by the attention network
+    a_p = w2 . relu(w1 h_p + b1) (w1 [A, dim], b1 [A], w2 [A]), the scores are softmax-normalised over the sample's pairs and the pair vectors
+    pooled by those weights -> [B, dim].  No [B, P, dim] or [B, P, A] tensor, forward or backward: the scores are a GEMM on the matrix cores
+    whose operand is multiplied out in registers, the backward recomputes them from x, the parameters, out and the log-sum-exp
+    (nrx_afm_fwd / _bwd; the header spells out every fp32 chain).  field_off as dot_interaction's.  On the GPU with fp32 tensors, a supported
+    shape (afm_supported) and fields at multiples of 4 columns the fused kernels run, on the current stream with no host synchronisation
+    (graph-capturable; the same bits run to run); anything else takes afm_pool_math.  A row-strided view (unit column stride, row stride
+    % 4 == 0, 16-byte aligned) is read in place, anything else through one contiguous copy.  The gradient of x is zero outside the fields."""
+    dim = int(dim)
+    offs = _dot_fields(field_off, dim, "afm_pool")
+    A = _afm_params(dim, w1, b1, w2, "afm_pool")
+    if x.dim() != 2:
+        raise ValueError(f"afm_pool: expected x [batch, width], got {tuple(x.shape)}")
+    if any(o < 0 or o + dim > x.shape[1] for o in offs):
+        raise ValueError(f"afm_pool: a field of dim {dim} leaves the {x.shape[1]} columns of x (field_off {list(offs)})")
+    if (not x.is_cuda or x.dtype != torch.float32 or any(t.dtype != torch.float32 or t.device != x.device for t in (w1, b1, w2))
+            or any(o % 4 != 0 for o in offs) or not afm_supported(len(offs), dim, A)):
+        return afm_pool_math(x, offs, dim, w1, b1, w2)
+    x = _rows16(x, "afm_pool: x")
+    W = x.shape[1]
+    ld = x.stride(0) if x.shape[0] > 1 else W
+    if ld % 4 != 0:          # (a contiguous x whose width is no multiple of 4: the one copy, with the row stride the kernels need)
+        ld = W + (-W) % 4
+        x = torch.nn.functional.pad(x, (0, ld - W))[:, :W]
+    return _AfmFn.apply(x, offs, dim, ld, w1, b1, w2)
 
 
 # ------------------------------------------------------------------------------- ItemCF recall (csrc/nrx_itemcf.hip, DESIGN 7f)

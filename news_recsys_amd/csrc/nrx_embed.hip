@@ -1068,16 +1068,23 @@ __global__ __launch_bounds__(NRX_BLOCK) void embed_bwd_sorted_kernel(const Sorte
                 scale = nrx_gconst<float>(a->f[fi].weight)[r];
             }
             const int wide_col = a->f[fi].wide_col, out_col = a->f[fi].out_col;
+            const bool fm = a->g_fm != nullptr && a->f[fi].fm;           // (the FM term, as in the loop above: it was missing here)
+            const float gf = fm ? nrx_gconst<float>(a->g_fm)[b] : 0.f;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int k = k0 + j;
                 if (k < D) {
                     float g;
-                    if (wide_col >= 0)
+                    if (wide_col >= 0) {
                         g = (k == 0) ? (a->g_wide ? nrx_gconst<float>(a->g_wide)[b * a->wide_ld + wide_col] : 0.f)
                                      : (a->g_out ? nrx_gconst<float>(a->g_out)[b * a->out_ld + out_col + k - 1] : 0.f);
-                    else
+                    } else {
                         g = a->g_out ? nrx_gconst<float>(a->g_out)[b * a->out_ld + out_col + k] : 0.f;
+                        if (fm)
+                            g += (k == 0) ? gf
+                                          : gf * (nrx_gconst<float>(a->fm_sums)[b * a->sums_ld + k] -
+                                                  nrx_gconst<float>(a->feat)[b * a->feat_ld + out_col + k]);
+                    }
                     ac[j] += g * scale;
                 }
             }

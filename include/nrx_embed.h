@@ -1195,6 +1195,54 @@ NRX_API int nrx_afm_bwd(const float* x, int64_t ld, const int32_t* field_off /* 
                      const float* g_out, int64_t g_out_ld, float* g_x, int64_t gx_ld, float* g_W1, float* g_b1, float* g_w2, void* workspace,
                      void* stream);
 
+/* ---- one interacting layer of AutoInt: multi-head self-attention over the fields (Song et al. CIKM 2019) --------------------------
+ * x: fp32 [batch, ld]; field i of sample b is x_i = x[b * ld + field_off[i] .. + din) (the nrx_afm_fwd convention: 16-byte aligned, not
+ * overlapping, neither adjacent nor ordered; field_off is a HOST array).  Wq, Wk, Wv [C, din] fp32 row-major, contiguous (nn.Linear.weight, no
+ * bias), Wres [C, din] or NULL; C = heads * head_dim; head h owns the columns [h head_dim, (h + 1) head_dim) of q, k, v.
+ *   forward : q_i[c] = chain from 0 over d = 0 .. din - 1 ascending:  acc = fmaf(Wq[c, d], x_i[d], acc)   (v_mfma_f32_32x32x2_f32 takes d in
+ *             pairs; din is even); k, v and r (Wres; r = 0 when it is NULL) alike.
+ *             t_ij = chain from 0 over c ascending within the head of fmaf(k_j[c], q_i[c], .);  s_ij = fl(scale * t_ij), over ALL j (j = i too).
+ *             m_i = max_j s_ij;  E_ij = expf(fl(s_ij - m_i)) (the device library's expf, within 1 ulp; the compiler may fuse scale * t - m into
+ *             one fma, which drops a rounding);  l_i = fl(l_0 + l_1), l_k the sum from 0 of the E_ij with ((j >> 2) & 1) == k, ascending j
+ *             (an absent j < 32 ceil(F / 32) adds 0);  row_lse[(b * heads + h) * F + i] = fl(m_i + logf(l_i)).
+ *             o_i[c] = fl(a / l_i), a the chain from 0 over j in the order 0, 4, 1, 5, 2, 6, 3, 7, 8, 12, 9, 13, .. (j = (s & 3) + 8 (s >> 2) + 4 k,
+ *             s = 0 .. 15, k = 0, 1, then the same from 32 on) of fmaf(v_j[c], E_ij, .);
+ *             out[b * out_ld + i * C + c] = max(fl(o_i[c] + r_i[c]), 0)   (o_i[c] when Wres is NULL).
+ *   backward (from x, the weights, out, row_lse and g_out alone; q, k, v and the weights p recomputed by the chains above; nothing of size
+ *             batch * F * F or batch * F * C exists):  dO_i[c] = out[b, i C + c] > 0 ? g_out[b * g_out_ld + i C + c] : 0  -- the ReLU mask is
+ *             `out > 0` of the buffer handed in; dR = dO.
+ *             p_ij = expf(fl(s_ij - row_lse));  dP_ij = chain from 0 over c ascending of fmaf(v_j[c], dO_i[c], .);
+ *             delta_i = fl(e_0 + e_1), e_k the chain from 0 over the j with ((j >> 2) & 1) == k ascending of fmaf(p_ij, dP_ij, .);
+ *             dS_ij = fl(p_ij * fl(dP_ij - delta_i));
+ *             dq_i[c] = fl(scale * chain from 0 over j in the order above of fmaf(k_j[c], dS_ij, .));
+ *             dk_j[c] = fl(scale * chain from 0 over i in that order of fmaf(q_i[c], dS_ij, .));  dv_j[c] = chain over i of fmaf(dO_i[c], p_ij, .).
+ *             g_x[b * gx_ld + field_off[i] + d] = one chain from 0 over the matrices (q, k, v, res) and within each over c ascending of
+ *             fmaf(W[c, d], dM_i[c], .), dM = dq, dk, dv, dR: complete (the caller adds nothing); the field columns only are written.
+ *             g_Wq, g_Wk, g_Wv, g_Wres in SLICES of nrx_autoint_wgrad_slice(F, din, heads, head_dim) samples (a function of the shape alone):
+ *             slice s covers the samples [s SL, min((s + 1) SL, batch)), its partial is one chain from 0 over (b ascending, i ascending) of
+ *             fmaf(dM_i[c], x_i[d], .) (an odd F appends one term of zeros per sample); g = ((part_0 + part_1) + part_2) + .. in slice order
+ *             (a second launch; no atomics).  workspace: nrx_autoint_bwd_workspace(batch, F, din, heads, head_dim) device bytes, 4-byte
+ *             aligned.  g_Wres must be NULL exactly when Wres is, and is then not touched.
+ * out, row_lse and g_x are functions of the one sample: their bits depend neither on batch, nor on the sample's place in it, nor on the grid;
+ * the parameter gradients are the same bits run to run.  One owner per output element, no float atomics; nothing outside the stated outputs
+ * is written (pad columns, the columns of a g_x row outside every field, bytes past the workspace).  No allocation, copy or synchronisation:
+ * capturable.  x: 16-byte aligned, ld % 4 == 0; every other pointer 4-byte aligned; out_ld, g_out_ld >= F C; gx_ld holds every field.
+ * nrx_autoint_supported(F, din, heads, head_dim): 1 for F in 2..64, din a multiple of 4 in 4..64, head_dim a multiple of 4, C in 4..64, else 0
+ * -- outside it the launch entry points return NRX_ERR_UNSUPPORTED with nothing enqueued.  Null or misaligned pointers, strides below what
+ * they must hold, overlapping or out-of-row fields, a scale that is not finite, a count < 1: NRX_ERR_BAD_ARG before any launch,
+ * nrx_last_error() naming the argument.  batch == 0: NRX_OK, nothing launched. */
+NRX_API int nrx_autoint_supported(int32_t n_fields, int32_t din, int32_t heads, int32_t head_dim);
+NRX_API int64_t nrx_autoint_wgrad_slice(int32_t n_fields, int32_t din, int32_t heads, int32_t head_dim);
+NRX_API int64_t nrx_autoint_bwd_workspace(int64_t batch, int32_t n_fields, int32_t din, int32_t heads, int32_t head_dim);
+NRX_API int nrx_autoint_layer_fwd(const float* x, int64_t ld, const int32_t* field_off /* HOST, n_fields */, int32_t n_fields, int32_t din,
+                     const float* Wq, const float* Wk, const float* Wv, const float* Wres /* or NULL */, int32_t heads, int32_t head_dim,
+                     float scale, int64_t batch, float* out, int64_t out_ld, float* row_lse, void* stream);
+NRX_API int nrx_autoint_layer_bwd(const float* x, int64_t ld, const int32_t* field_off /* HOST, n_fields */, int32_t n_fields, int32_t din,
+                     const float* Wq, const float* Wk, const float* Wv, const float* Wres /* or NULL */, int32_t heads, int32_t head_dim,
+                     float scale, int64_t batch, const float* out, int64_t out_ld, const float* row_lse, const float* g_out, int64_t g_out_ld,
+                     float* g_x, int64_t gx_ld, float* g_Wq, float* g_Wk, float* g_Wv, float* g_Wres /* NULL iff Wres is */, void* workspace,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -228,6 +228,12 @@ SIGNATURES = {
     "nrx_afm_bwd_workspace": (_i64, [_i64, _i32, _i32, _i32]),
     "nrx_afm_fwd": (C.c_int, [_p, _i64, C.POINTER(_i32), _i32, _i32, _p, _p, _p, _i32, _i64, _p, _i64, _p, _p]),
     "nrx_afm_bwd": (C.c_int, [_p, _i64, C.POINTER(_i32), _i32, _i32, _p, _p, _p, _i32, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p]),
+    "nrx_autoint_supported": (C.c_int, [_i32, _i32, _i32, _i32]),
+    "nrx_autoint_wgrad_slice": (_i64, [_i32, _i32, _i32, _i32]),
+    "nrx_autoint_bwd_workspace": (_i64, [_i64, _i32, _i32, _i32, _i32]),
+    "nrx_autoint_layer_fwd": (C.c_int, [_p, _i64, C.POINTER(_i32), _i32, _i32, _p, _p, _p, _p, _i32, _i32, C.c_float, _i64, _p, _i64, _p, _p]),
+    "nrx_autoint_layer_bwd": (C.c_int, [_p, _i64, C.POINTER(_i32), _i32, _i32, _p, _p, _p, _p, _i32, _i32, C.c_float, _i64, _p, _i64, _p, _p, _i64, _p,
+                                        _i64, _p, _p, _p, _p, _p, _p]),
     "nrx_rep_pack": (C.c_int, [C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_i64), C.POINTER(_i32), _i32, C.POINTER(_i64),
                                C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32), _i32, _i32, _i64, _i64, _p, _p]),
     "nrx_rep_ordered_sum": (C.c_int, [_p, _i32, _i64, _i64, _p, _p]),

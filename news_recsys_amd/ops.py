@@ -16,6 +16,7 @@ Operator                          replaces (reference file:line)
   dot_interaction / dot_interaction_cat_   (new: pairwise dot-product interaction of PNN / DLRM)
   cin / cin_math                   (new: Compressed Interaction Network of xDeepFM)
   afm_pool / afm_pool_math         (new: attentional pooling of pairwise field interactions, AFM)
+  interacting_layer / interacting_layer_math   (new: multi-head self-attention over the fields, AutoInt)
   itemcf_similarity / itemcf_recall  compute_item_similarity / recall_top_k_items  recall/ItemCF/itemCF_base.py:18-58
 """
 from __future__ import annotations
@@ -3583,6 +3584,124 @@ def afm_pool(x: torch.Tensor, field_off, dim: int, w1: torch.Tensor, b1: torch.T
         ld = W + (-W) % 4
         x = torch.nn.functional.pad(x, (0, ld - W))[:, :W]
     return _AfmFn.apply(x, offs, dim, ld, w1, b1, w2)
+
+
+# ------------------------------------------------------------------------------- AutoInt's interacting layer (csrc/nrx_autoint.hip)
+AUTOINT_MAX = 64                 # F, din, C = heads * head_dim
+autoint_calls = 0                # forward launches of nrx_autoint_layer_fwd so far (tests assert the model took the fused path)
+
+
+def interacting_layer_supported(n_fields: int, din: int, heads: int, head_dim: int) -> bool:
+    """The shapes nrx_autoint_layer_fwd / _bwd take (nrx_autoint_supported; anything else is NRX_ERR_UNSUPPORTED there)."""
+    return (2 <= n_fields <= AUTOINT_MAX and 4 <= din <= AUTOINT_MAX and din % 4 == 0 and heads >= 1 and head_dim >= 4 and head_dim % 4 == 0
+            and heads * head_dim <= AUTOINT_MAX)
+
+
+def _autoint_params(din: int, wq, wk, wv, wres, heads: int, what: str) -> int:
+    if isinstance(heads, bool) or not isinstance(heads, (int, np.integer)) or heads < 1:
+        raise ValueError(f"{what}: heads must be a positive integer, got {heads!r}")
+    if wq.dim() != 2 or wq.shape[1] != din or wq.shape[0] < 1:
+        raise ValueError(f"{what}: wq must be [C, {din}], got {tuple(wq.shape)}")
+    Cw = int(wq.shape[0])
+    for name, w in (("wk", wk), ("wv", wv), ("wres", wres)):
+        if w is not None and tuple(w.shape) != (Cw, din):
+            raise ValueError(f"{what}: {name} must be [{Cw}, {din}] like wq, got {tuple(w.shape)}")
+    if Cw % heads != 0:
+        raise ValueError(f"{what}: the {Cw} rows of wq do not split into {heads} heads")
+    return Cw
+
+
+def interacting_layer_math(x: torch.Tensor, field_off, din: int, wq: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor,
+                           wres: Optional[torch.Tensor] = None, heads: int = 1, scale: float = 1.0) -> torch.Tensor:
+    """interacting_layer's definition in plain torch, on any device and in the dtype of x (the fallback, the float64 restatement and the
+    yardstick): the projections of the stacked fields, softmax(scale q k^T) v per head over all fields, the residual projection, ReLU ->
+    [B, F * C].  Differentiable by autograd.  Materialises [B, F, C] four times and [B, heads, F, F]."""
+    din = int(din)
+    offs = _dot_fields(field_off, din, "interacting_layer_math")
+    Cw = _autoint_params(din, wq, wk, wv, wres, heads, "interacting_layer_math")
+    e = torch.stack([x[:, o:o + din] for o in offs], dim=1)
+    B, F = e.shape[0], len(offs)
+    hd = Cw // heads
+    q, k, v = ((e @ w.to(x.dtype).t()).view(B, F, heads, hd).transpose(1, 2) for w in (wq, wk, wv))
+    p = torch.softmax((q @ k.transpose(-1, -2)) * scale, dim=-1)
+    o = (p @ v).transpose(1, 2).reshape(B, F, Cw)
+    if wres is not None:
+        o = o + e @ wres.to(x.dtype).t()
+    return torch.relu(o).reshape(B, F * Cw)
+
+
+class _AutoIntFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, offs, din, ld, heads, scale, wq, wk, wv, wres):
+        global autoint_calls
+        lib = _lib.load()
+        B, F, Cw = x.shape[0], len(offs), wq.shape[0]
+        ws = [_f32c(t.detach(), "interacting_layer: weights") for t in (wq, wk, wv)]
+        wr = None if wres is None else _f32c(wres.detach(), "interacting_layer: weights")
+        out = torch.empty((B, F * Cw), dtype=torch.float32, device=x.device)
+        lse = torch.empty((B, heads, F), dtype=torch.float32, device=x.device)
+        check(lib.nrx_autoint_layer_fwd(x.data_ptr(), ld, _dot_off_array(offs), F, din, ws[0].data_ptr(), ws[1].data_ptr(), ws[2].data_ptr(), _ptr(wr),
+                                        heads, Cw // heads, scale, B, out.data_ptr(), F * Cw, lse.data_ptr(), _stream_ptr(x)), "nrx_autoint_layer_fwd")
+        autoint_calls += 1
+        ctx.save_for_backward(x, out, lse, *ws, *(() if wr is None else (wr,)))
+        ctx.cfg = (offs, din, ld, heads, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        lib = _lib.load()
+        offs, din, ld, heads, scale = ctx.cfg
+        x, out, lse, wq, wk, wv = ctx.saved_tensors[:6]
+        wr = ctx.saved_tensors[6] if len(ctx.saved_tensors) > 6 else None
+        B, Wd = x.shape
+        F, Cw = len(offs), wq.shape[0]
+        g = _f32c(g_out if g_out.dtype == torch.float32 else g_out.float(), "interacting_layer: grad")
+        # the columns of x outside every field take no part: their gradient is 0 (the kernel writes the field columns only)
+        covered = F * din == Wd
+        g_x = torch.empty((B, Wd), dtype=torch.float32, device=x.device) if covered else torch.zeros((B, Wd), dtype=torch.float32, device=x.device)
+        fresh = torch.empty_like if B > 0 else torch.zeros_like          # (an empty batch launches nothing: its weight gradients are zeros)
+        gq, gk, gv = fresh(wq), fresh(wk), fresh(wv)
+        gr = None if wr is None else fresh(wr)
+        wsp = torch.empty((lib.nrx_autoint_bwd_workspace(B, F, din, heads, Cw // heads) + 3) // 4, dtype=torch.float32, device=x.device)
+        check(lib.nrx_autoint_layer_bwd(x.data_ptr(), ld, _dot_off_array(offs), F, din, wq.data_ptr(), wk.data_ptr(), wv.data_ptr(), _ptr(wr), heads,
+                                        Cw // heads, scale, B, out.data_ptr(), F * Cw, lse.data_ptr(), g.data_ptr(), g.shape[1], g_x.data_ptr(), Wd,
+                                        gq.data_ptr(), gk.data_ptr(), gv.data_ptr(), _ptr(gr), wsp.data_ptr(), _stream_ptr(x)), "nrx_autoint_layer_bwd")
+        return g_x, None, None, None, None, None, gq, gk, gv, gr
+
+
+def interacting_layer(x: torch.Tensor, field_off, din: int, wq: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor,
+                      wres: Optional[torch.Tensor] = None, heads: int = 1, scale: float = 1.0) -> torch.Tensor:
+    """One interacting layer of AutoInt (Song et al. CIKM 2019): x [B, W] holds the F fields x_i = x[:, field_off[i] : field_off[i] + din];
+    q, k, v = wq x_i, wk x_i, wv x_i (weights [C, din], the layout of nn.Linear.weight, no bias; C = heads * head_dim), every head attends
+    over ALL fields with softmax(scale <q_i, k_j>), the heads' outputs are concatenated, the residual projection wres x_i (if given) is added
+    and a ReLU applied -> [B, F * C], field i at the columns [i C, (i + 1) C).  No q / k / v tensor and nothing of size B x F x F in global
+    memory, forward or backward: projections and attention are GEMMs on the matrix cores over operands in LDS, the backward recomputes them
+    from x, the weights, out and the rows' log-sum-exp (nrx_autoint_layer_fwd / _bwd; the header spells out every fp32 chain).  field_off as
+    dot_interaction's.  On the GPU with fp32 tensors, a supported shape (interacting_layer_supported) and fields at multiples of 4 columns
+    the fused kernels run, on the current stream with no host synchronisation (graph-capturable; the same bits run to run); anything else
+    takes interacting_layer_math.  A row-strided view (unit column stride, row stride % 4 == 0, 16-byte aligned) is read in place, anything
+    else -- a contiguous x whose width is no multiple of 4 among them -- through one copy.  The gradient of x is zero outside the fields."""
+    din = int(din)
+    offs = _dot_fields(field_off, din, "interacting_layer")
+    Cw = _autoint_params(din, wq, wk, wv, wres, heads, "interacting_layer")
+    heads, scale = int(heads), float(scale)
+    if x.dim() != 2:
+        raise ValueError(f"interacting_layer: expected x [batch, width], got {tuple(x.shape)}")
+    if any(o < 0 or o + din > x.shape[1] for o in offs):
+        raise ValueError(f"interacting_layer: a field of din {din} leaves the {x.shape[1]} columns of x (field_off {list(offs)})")
+    if not math.isfinite(scale):
+        raise ValueError(f"interacting_layer: scale must be finite, got {scale}")
+    ws = [w for w in (wq, wk, wv, wres) if w is not None]
+    if (not x.is_cuda or x.dtype != torch.float32 or any(t.dtype != torch.float32 or t.device != x.device for t in ws)
+            or any(o % 4 != 0 for o in offs) or not interacting_layer_supported(len(offs), din, heads, Cw // heads)):
+        return interacting_layer_math(x, offs, din, wq, wk, wv, wres, heads, scale)
+    x = _rows16(x, "interacting_layer: x")
+    W = x.shape[1]
+    ld = x.stride(0) if x.shape[0] > 1 else W
+    if ld % 4 != 0:          # (a contiguous x whose width is no multiple of 4: the one copy, with the row stride the kernels need)
+        ld = W + (-W) % 4
+        x = torch.nn.functional.pad(x, (0, ld - W))[:, :W]
+    return _AutoIntFn.apply(x, offs, din, ld, heads, scale, wq, wk, wv, wres)
 
 
 # ------------------------------------------------------------------------------- ItemCF recall (csrc/nrx_itemcf.hip, DESIGN 7f)

@@ -853,6 +853,9 @@ def shard_model_step_(model, rank: int, world: int, group=None, host_staged: boo
     if getattr(model, "afm_cfg", None) is not None:
         raise NotImplementedError("shard_model_step_: a model with afm_cfg (sort/afm: attentional pooling of pair interactions) is not supported -- the "
                                   "bound step does not know that operator")
+    if getattr(model, "autoint_cfg", None) is not None:
+        raise NotImplementedError("shard_model_step_: a model with autoint_cfg (sort/autoint: self-attention over the fields) is not supported -- the "
+                                  "bound step does not know that operator")
     is_bf16 = [e.weight.dtype is torch.bfloat16 for e in model.embedding_tables.values()]
     if any(is_bf16) and not bf16_tables:
         raise NotImplementedError("shard_model_step_: the model's embedding tables are bf16 (embeddings.table_dtype: bf16): pass bf16_tables=True "

@@ -1075,6 +1075,9 @@ def shard_model_(model, rank: int, world: int, group=None, backend=None):
     if getattr(model, "afm_cfg", None) is not None:
         raise NotImplementedError("shard_model_: a model with afm_cfg (sort/afm: attentional pooling of pair interactions) is not supported -- the "
                                   "bound step does not know that operator")
+    if getattr(model, "autoint_cfg", None) is not None:
+        raise NotImplementedError("shard_model_: a model with autoint_cfg (sort/autoint: self-attention over the fields) is not supported -- the "
+                                  "bound step does not know that operator")
     if any(e.weight.dtype is torch.bfloat16 for e in model.embedding_tables.values()):
         raise NotImplementedError("shard_model_: bf16 embedding tables are not supported here -- its backward forms dense shard gradients, which "
                                   "bf16 tables never have; the bound step trains them: shard_step.shard_model_step_(..., bf16_tables=True)")
